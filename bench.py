@@ -1,17 +1,26 @@
 #!/usr/bin/env python
 """bench.py — env steps/s of the MI355X-native Jitterbug stepper (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one control step (50 physics substeps + reward + observation, in-kernel auto-reset) of every
 environment of the batch.  Workload at N=1: BASELINE.json configs[2] — move_from_origin, 4096 envs, full
-contact solve (configs[1], contacts off, is reported alongside in "also").  For N>1 (launched by
+contact solve (configs[1], contacts off, is reported alongside in "also" under --full).  For N>1 (launched by
 torch.distributed.run, one rank per GPU) each rank steps its own 4096 envs (weak scaling; env indices are
 global so results do not depend on the split) and rank 0 gathers [N_local, D+2] obs/reward/done rows over
 RCCL every step, inside the timed region.
 
 Inputs (actions) are resident in HBM before the timed region; the timed region is K launches bracketed by
 barrier + torch.cuda.synchronize(); rank 0 prints ONE JSON line.
+
+A plain run measures the headline and nothing else: set up, W warm-up steps, K timed steps, the line.  --full adds what is
+measured next to it in the same process (steady-state and whole-episode windows, fused rollouts, contacts off, host-buffer
+rates, the CPU baseline); --no-steady / --no-also / --no-host-rate / --no-cpu-baseline leave parts of that out again.
+
+--dump-outputs DIR writes what the timed path returned at its last step - obs [N, D], reward [N], done [N] (rank 0: the
+gathered rows of every rank for N>1) - as DIR/obs.npy, DIR/reward.npy, DIR/done.npy in float32.  Actions and resets are
+seeded (--seed), so two builds run with the same arguments can be compared output for output.  Above 64 MB in all, a fixed
+seeded sample of env rows is written instead, with their indices in DIR/env_index.npy.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts ITSELF: the parent spawns
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (the counterpart of the reference's
@@ -31,6 +40,7 @@ if ROOT not in sys.path:
 ALGO_BYTES_PER_ENV_STEP = 317       # read qpos 64 + qvel 60 + ctrl 4; write qpos 64 + qvel 60 + obs 60 + reward 4 + done 1
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: 8.0 TB/s spec
 N_ENVS_PER_GPU = 4096
+DUMP_LIMIT_BYTES = 64 << 20         # --dump-outputs: at most this much in all
 TASK = "move_from_origin"
 
 
@@ -178,7 +188,12 @@ def main(argv=None):
     ap.add_argument("--task", default=TASK, help="default move_from_origin (the BASELINE metric); move_to_pose is BASELINE configs[3]'s task")
     ap.add_argument("--augmented", action="store_true", help="one randomised model per env (BASELINE configs[4], augment_Jitterbug semantics)")
     ap.add_argument("--no-steady", action="store_true", help="skip the steady-state (steps 100-400) and full-episode blocks measured next to the headline")
+    ap.add_argument("--full", action="store_true", help="measure everything next to the headline as well (steady / full episode / fused rollouts / also / host-buffer rate / CPU baseline); "
+                                                        "without it a run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed path's last-step obs / reward / done to DIR/<name>.npy (float32)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # which step kernel: resolved by the PRODUCT (jitterbug_amd.variants - this script holds no threshold of its own); --lean / --no-lean force one
     variant = "lean" if args.lean else "ordinary" if args.no_lean else "auto"
     task = args.task
@@ -267,7 +282,7 @@ def main(argv=None):
     D = model.OBS_DIM[task]
     K, W = args.steps, args.warmup
 
-    def run(contacts, steps, warmup, gather):
+    def run(contacts, steps, warmup, gather, dump=False):
         """One timed run.  Every rank passes the same three sync points whatever happens to it, so ranks whose gather path raises (its
         first run over real links, say) leave this run together - RanksDisagree - and nobody is left in a barrier.  (A rank that fails
         alone INSIDE a collective still leaves the others waiting in it: that ends at the process group's timeout / the launcher's
@@ -282,7 +297,7 @@ def main(argv=None):
         except Exception:
             close_quietly(setup)
             raise
-        env, sh, one, drain, obs, last = setup
+        env, sh, one, drain, obs, last, outs = setup
         t0 = time.perf_counter()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         try:
@@ -301,7 +316,7 @@ def main(argv=None):
             close_quietly(setup)          # a failed attempt leaves no communicator, stream or handle behind before the next mode is tried
             raise
         try:
-            out = run_finish(env, sh, obs, last, wall, ev0.elapsed_time(ev1))
+            out = run_finish(env, sh, obs, last, wall, ev0.elapsed_time(ev1), outs if dump else None)
         except Exception as e:
             failure, out = e, None
             close_quietly(setup)
@@ -373,7 +388,7 @@ def main(argv=None):
             one(i)
         drain()
         finite_warm[0] = bool(torch.isfinite(sh.last_local_rows() if (sh is not None and warmup) else obs).all().item()) if warmup else True
-        return env, sh, one, drain, obs, last
+        return env, sh, one, drain, obs, last, (obs, rew, done)
 
     finite_warm = [True]
 
@@ -386,7 +401,8 @@ def main(argv=None):
             nccl_group[0] = dist.new_group(backend="nccl")
         return nccl_group[0]
 
-    def run_finish(env, sh, obs, last, wall, dev_ms):
+    def run_finish(env, sh, obs, last, wall, dev_ms, outs=None):
+        """outs: this run's (obs, reward, done) buffers when its last step is to be written out (--dump-outputs)"""
         sc, ep, cap = env.counters()
         lastrows = sh.last_local_rows()[:, :D] if sh is not None else obs
         finite = finite_warm[0] and bool(torch.isfinite(lastrows).all().item())      # checked after the warm-up and after the timed steps
@@ -394,16 +410,33 @@ def main(argv=None):
         if sh is not None and rank == 0:                # the gathered block of the last step really holds every rank's rows
             ob_all, rw_all, dn_all = last[0].get()
             finite = finite and ob_all.shape[0] == n * world and bool(torch.isfinite(ob_all).all().item()) and bool((ob_all[:n] == sh.last_local_rows()[:, :D]).all().item())
+            if outs is not None:
+                outs = (ob_all, rw_all, dn_all)           # what a caller of the sharded path receives on rank 0: every rank's rows
+        if outs is not None and rank == 0:
+            write_outputs(dict(zip(("obs", "reward", "done"), outs)))          # before close(): the gathered rows live in the env's buffers
         if sh is not None:
             sh.close()          # flush, both streams idle, the library's communicator destroyed (cabi), then the env
         else:
             env.close()
         return wall, dev_ms, float(cap.sum()), finite
 
+    def write_outputs(arrays):
+        """DIR/<name>.npy in float32; above DUMP_LIMIT_BYTES in all, the same fixed seeded sample of env rows from every array"""
+        host = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+        rows = next(iter(host.values())).shape[0]
+        per_row = sum(a.nbytes for a in host.values()) // rows
+        if rows * per_row > DUMP_LIMIT_BYTES:
+            pick = np.sort(np.random.default_rng(0).choice(rows, DUMP_LIMIT_BYTES // (per_row + 8), replace=False))
+            host = {k: a[pick] for k, a in host.items()}
+            host["env_index"] = pick.astype(np.float64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, a in host.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
+
     measured = None
     while True:
         try:
-            measured = run(args.contacts, K, W, gather=use_gather)
+            measured = run(args.contacts, K, W, gather=use_gather, dump=args.dump_outputs is not None)
             break
         except RanksDisagree as e:
             if use_gather is None:
@@ -428,7 +461,7 @@ def main(argv=None):
     #   steady        100 warm-up + 300 timed steps (steps 100-400 of the episode; the window the committed rocprofv3 profile covers)
     #   full_episode  0 + 1000 steps from the reset, including the in-kernel auto-reset of the last step
     steady = full_episode = None
-    if not args.no_steady:
+    if args.full and not args.no_steady:
         ws, ds, _, fs = run(args.contacts, 300, 100, gather=use_gather)
         ws = rank_max(ws)
         steady = {"value": total_envs * 300 / ws, "unit": "env steps/s", "ms_per_step": ws * 1e3 / 300, "launch_ms": ds / 300, "steps": 300, "warmup": 100,
@@ -443,7 +476,7 @@ def main(argv=None):
     # launches), the in-kernel heuristic policy instead of the tape, and the motor-flat-out tape.  Its bound is the slowest wave's SUM
     # over the K steps, measured by the kernel itself (jb_wave_clocks: s_memrealtime per wave) and reported against the mean wave.
     rollout_fused = None
-    if not args.no_steady and world == 1 and dist is None:
+    if args.full and not args.no_steady and world == 1 and dist is None:
         def fused(k_launch, source, total=1000, episodes=1):
             g = torch.Generator(device=dev)
             g.manual_seed(1234 + rank + 7919 * args.seed)
@@ -496,7 +529,7 @@ def main(argv=None):
     # N > 1: the same fused rollout across the shards (ShardedJitterbugEnv.rollout: K steps in one launch per rank, then ONE gather of the
     # [K, N_local, D+2] blocks - a hundred times fewer, a hundred times larger collectives than the per-step path).  Next to the headline,
     # never instead of it; a failure here is recorded, it does not take the line down.
-    if not args.no_steady and dist is not None and use_gather:
+    if args.full and not args.no_steady and dist is not None and use_gather:
         # every rank passes the same sync points whatever happens to it (like run()): a rank that fails alone brings its failure to the next
         # sync point instead of leaving the others in it
         failure, sh, tape = None, None, None
@@ -547,13 +580,13 @@ def main(argv=None):
         return "not a BASELINE config"
 
     also = None
-    if not args.no_also and world == 1:
+    if args.full and not args.no_also and world == 1:
         w2, d2, _, _ = run(1 - args.contacts, max(50, K // 5), 20, gather=False)
         also = {"workload": "%s N_envs=%d contacts %s (%s)" % (task, n, "off" if args.contacts else "on", config_label(1 - args.contacts)),
                 "value": n * max(50, K // 5) / w2, "unit": "env steps/s"}
 
     host_rate = None
-    if world == 1 and not args.no_host_rate:
+    if args.full and world == 1 and not args.no_host_rate:
         # the reference-shaped entry point jb_step (host pointers: H2D actions, D2H obs/reward/done, stream sync per step) on the same
         # workload, for the record next to `value` (which has inputs resident in HBM): the PCIe-inclusive rate
         import numpy as np
@@ -665,7 +698,7 @@ def main(argv=None):
             "metric": "env steps/s at N_envs=%d, %s" % (n, task),
             "value": None if degraded else value, "unit": "env steps/s", "n_gpus": world, "steps": K, "warmup": W,
             "ms_per_step": wall_max * 1e3 / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": "%s, N_envs=%d per GPU, %s, 50 substeps/step, in-kernel auto-reset (%s)"
                                    % (task + (", one randomised model per env" if args.augmented else ""), n, ("full Newton contact solve" if args.contacts else "contacts off") + {"ordinary": "", "pair": ", PAIR kernel variant (floor + mass / upper-leg contact)", "lean": ", LEAN kernel variant (two waves per SIMD)", "lean_pair": ", LEAN + PAIR kernel variant (two waves per SIMD, one model per env)"}[used_variant[0]], config_label(args.contacts)),
                        "global_envs": total_envs, "parallelism": "env-sharded x%d%s" % (world, gather_txt)},
@@ -697,7 +730,7 @@ def main(argv=None):
             res["also"] = also
         if host_rate:
             res["host_buffer_rate"] = host_rate
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cores = usable_cores()
             res["cpu_baseline"] = cpu_baseline(cores, task)
         print(json.dumps(res))

@@ -70,7 +70,7 @@ def test_no_exec_in_bench():
 
 @pytest.mark.gpu
 def test_bench_line_names_the_baseline_workload_and_the_loaded_library():
-    p = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-also", "--no-host-rate"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    p = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-also", "--no-host-rate"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -93,6 +93,47 @@ def test_bench_line_names_the_baseline_workload_and_the_loaded_library():
     assert 0 < wc["mean_over_slowest"] <= 1 and rf["k1000"]["value"] <= wc["ceiling_mean_wave"] * 1.02
     assert rf["k1000"]["value"] > 1.05 * d["value_full_episode"]          # what the fused launch is for (measured: 6.3 -> 7.5-8.3 M env-steps/s: it lasts as long as the wave whose robot tips over first)
     assert len(rf["k1000"]["ms_per_step_by_episode"]) == 3
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without --full a run times the headline steps and nothing next to them.  --dump-outputs writes the timed path's obs / reward / done of
+    its last step (warm-up + --steps steps of the seeded action stream from the seeded reset): two runs with the same arguments write the
+    same arrays, and so does the same path stepped here by hand."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        p = subprocess.run([sys.executable, BENCH, "--steps", "7", "--warmup", "3", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r["steps"] == 7 and r["warmup"] == 3 and r["full"] is False and r["finite"] is True and r["dtype"] == "f32" and r["higher_is_better"] is True
+        assert abs(r["ms_per_step"] - 4096 * 1e3 / r["value"]) <= 1e-9 * r["ms_per_step"]
+        assert not any(key in r for key in ("steady", "full_episode", "value_full_episode", "rollout_fused", "also", "host_buffer_rate", "cpu_baseline"))
+        arrays = {name: np.load(d / (name + ".npy")) for name in ("obs", "reward", "done")}
+        assert sorted(os.listdir(d)) == ["done.npy", "obs.npy", "reward.npy"]
+        assert arrays["obs"].shape == (4096, 15) and arrays["reward"].shape == (4096,) and arrays["done"].shape == (4096,)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values()) and set(np.unique(arrays["done"])) <= {0.0, 1.0}
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][name], dumps[1][name]) for name in ("obs", "reward", "done"))
+    import torch
+    from jitterbug_amd.vec_env import JitterbugVecEnv
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    actions = torch.rand((10, 4096), generator=g, device=dev, dtype=torch.float32) * 2 - 1
+    env = JitterbugVecEnv(4096, "move_from_origin", seed=0, device_id=0, variant="auto")
+    obs = torch.empty((4096, 15), device=dev); rew = torch.empty(4096, device=dev); done = torch.empty(4096, device=dev, dtype=torch.uint8)
+    torch.cuda.synchronize(dev)          # the handle steps on a stream of its own: the actions are written first
+    env.reset_device(None, obs.data_ptr())
+    for i in range(10):
+        env.step_device(actions[i].data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr())
+    env.synchronize()
+    env.close()
+    assert np.array_equal(dumps[0]["obs"], obs.cpu().numpy()) and np.array_equal(dumps[0]["reward"], rew.cpu().numpy())
+    assert np.array_equal(dumps[0]["done"], done.cpu().numpy().astype(np.float32))
 
 
 @pytest.mark.gpu
@@ -214,7 +255,7 @@ def test_bench_one_rank_through_the_librarys_own_collective():
     jb_gather_block_device - through real RCCL calls on a one-GPU box, and the line names the collective that ran."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"JB_BENCH_FORCE_DIST": "1", "WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29631"})
-    p = subprocess.run([sys.executable, BENCH, "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-also", "--no-host-rate", "--collective", "cabi", "--actions-from", "rank0"],
+    p = subprocess.run([sys.executable, BENCH, "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-also", "--no-host-rate", "--collective", "cabi", "--actions-from", "rank0"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

@@ -1,6 +1,7 @@
 """Model compiler known-answer tests (total mass, per-geom masses,
-hinge axes) and a cross-check of model_spec against the reference XML when it
-is mounted (never on the GPU box)."""
+hinge axes) and a cross-check of model_spec against the reference XML, through the
+elements of it that tests/golden/model_xml.json holds (tools/gen_golden_model_xml.py)."""
+import json
 import os
 import xml.etree.ElementTree as ET
 
@@ -9,7 +10,7 @@ import pytest
 
 from jitterbug_amd import model, model_spec
 
-REF_XML = "/root/reference/jitterbug_dmc/jitterbug.xml"
+GOLDEN_XML = os.path.join(os.path.dirname(__file__), "golden", "model_xml.json")
 
 
 def test_layout_matches_header():
@@ -77,10 +78,15 @@ def _floats(s):
     return [float(x) for x in s.split()]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason="reference not mounted")
+def _element(d):
+    el = ET.Element(d["tag"], d["attrib"])
+    el.extend(_element(c) for c in d["children"])
+    return el
+
+
 def test_spec_matches_reference_xml():
     """model_spec.SPEC restates jitterbug.xml number for number."""
-    root = ET.parse(REF_XML).getroot()
+    root = _element(json.load(open(GOLDEN_XML))["tree"])
     assert root.find("compiler").attrib["coordinate"] == "global"
     assert float(root.find("option").attrib["timestep"]) == model_spec.SPEC["timestep"]
     assert float(root.find("default/geom").attrib["density"]) == model_spec.DEFAULT_DENSITY

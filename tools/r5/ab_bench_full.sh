@@ -1,10 +1,10 @@
 # tools/r5/ab_bench_full.sh lib1.so lib2.so ... : the driver's bench line (steps 5-25 window + steady + full episode + fused blocks) for each build, on ONE box
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/r5
+OUT=${OUT:-bench_out/r5}; mkdir -p $OUT
 for lib in "$@"; do
   name=$(basename $lib .so)
-  JITTERBUG_HIP_LIB=$lib timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-host-rate > gpurun_out/r5/abfull_$name.json 2> gpurun_out/r5/abfull_$name.err || { tail -5 gpurun_out/r5/abfull_$name.err; continue; }
-  python3 - gpurun_out/r5/abfull_$name.json $name <<'PY'
+  JITTERBUG_HIP_LIB=$lib timeout -k 10 400 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-also --no-host-rate > $OUT/abfull_$name.json 2> $OUT/abfull_$name.err || { tail -5 $OUT/abfull_$name.err; continue; }
+  python3 - $OUT/abfull_$name.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
 rf = d["rollout_fused"]
