@@ -25,6 +25,7 @@
 #include "jb_model_build.hpp"
 #include "jb_model_compile.hpp"
 #include "jb_nominal_spec.h"
+#include "jb_owned.hpp"
 #include "jb_sim.hpp"
 #include "jb_step.hpp"
 #include "jb_task.hpp"
@@ -707,42 +708,54 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
         if (_e != hipSuccess) return fail(JB_E_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// The owners of the handle's memory (jb_owned.hpp): device buffers, pinned host buffers, an event (n = 1)
+struct HipDeviceMem {
+    template <typename T> static hipError_t alloc(T** p, size_t n) { return hipMalloc((void**)p, n * sizeof(T)); }
+    template <typename T> static void free(T* p) { (void)hipFree(p); }
+};
+struct HipPinnedMem {
+    template <typename T> static hipError_t alloc(T** p, size_t n) { return hipHostMalloc((void**)p, n * sizeof(T), hipHostMallocDefault); }
+    template <typename T> static void free(T* p) { (void)hipHostFree(p); }
+};
+struct HipEventApi {
+    static hipError_t alloc(hipEvent_t* e, size_t) { return hipEventCreateWithFlags(e, hipEventDisableTiming); }
+    static void free(hipEvent_t e) { (void)hipEventDestroy(e); }
+};
+template <typename T> using Dev = Owned<T*, HipDeviceMem>;
+template <typename T> using Pinned = Owned<T*, HipPinnedMem>;
+using Event = Owned<hipEvent_t, HipEventApi>;
+
 }  // namespace
 
+// Every member that owns memory is an owner: destroying the handle frees it, and the handle cannot be copied.  The raw pointers in ka
+// (and in the StepIO of a launch) are non-owning copies, refreshed wherever an owner is replaced.
 struct jb_handle {
     jb_config cfg;
     KArgs ka;
     int D;
     hipStream_t stream;
     bool own_stream;
-    float *d_root, *d_leg, *d_model, *d_ovc;
-    int* d_step; unsigned* d_episode;
-    // staging for the host-buffer entry points
-    float *d_action, *d_obs, *d_reward; unsigned char *d_done, *d_mask;
-    double *d_qpos, *d_qvel, *d_target;
-    unsigned long long* d_wave_stats;
-    unsigned long long* d_wave_clock;
-    unsigned long long* d_resolve;    // [1]: KArgs::resolve_count
-    float* d_capture; unsigned* d_capture_count;      // diagnostic builds (-DJB_CAPTURE)
-    float *d_tape, *d_rows_stage, *d_rew_stage;       // staging of the host-buffer rollouts (jb_step_many, jb_rollout_policy): grow-only, freed in jb_destroy
-    size_t tape_cap, rows_cap, rew_cap;               //   their capacities in floats
-    int* d_wave_order;               // launch order of the waves (jb_wave_order_kernel), null while the device holds the whole batch at once
+    Dev<float> d_root, d_leg, d_model, d_ovc;      // d_model: n_tables x LM_TABLE
+    Dev<int> d_step; Dev<unsigned> d_episode;
+    Dev<float> d_action, d_obs, d_reward; Dev<unsigned char> d_done, d_mask;      // staging for the host-buffer entry points
+    Dev<double> d_qpos, d_qvel, d_target;
+    Dev<unsigned long long> d_wave_stats, d_wave_clock, d_resolve;      // -DJB_WAVE_STATS builds; the last launch's wave lifetimes; [1]: KArgs::resolve_count
+    Dev<float> d_capture; Dev<unsigned> d_capture_count;      // diagnostic builds (-DJB_CAPTURE)
+    Dev<float> d_tape, d_rows_stage, d_rew_stage;      // staging of the host-buffer rollouts (jb_step_many, jb_rollout_policy): grow-only
+    Dev<int> d_wave_order;           // launch order of the waves (jb_wave_order_kernel), empty while the device holds the whole batch at once
     int wave_slots;                  // waves the device holds at once with this handle's kernel variant
-    size_t model_tables;
     EncArgs enc;          // observation encoder (n_layers = 0: none)
     PolicyParams<float> policy;      // keyword arguments of the reference's heuristic policies
-    JbNominalSpec* d_spec;           // nominal (uncompiled) model for the randomiser
+    Dev<JbNominalSpec> d_spec;       // nominal (uncompiled) model for the randomiser
     void* comm;                      // RCCL communicator (jb_comm_init), null until asked for
-    int comm_ranks, comm_rank;
-    int comm_nmax;                   // envs of the longest shard (jb_comm_set_shards); 0: every rank holds cfg.n_envs
+    int comm_ranks, comm_rank, comm_nmax;      // comm_nmax: envs of the longest shard (jb_comm_set_shards); 0: every rank holds cfg.n_envs
     // jb_step_async / jb_step_wait: pinned host staging (allocated at the first jb_step_async) and the event behind the D2H copies
-    float *p_action, *p_obs, *p_reward; unsigned char* p_done;
-    hipEvent_t async_done;
+    struct AsyncStage { Pinned<float> action, obs, reward; Pinned<unsigned char> done; Event copied; } async;
     bool async_pending;
-    float* d_terms;
-    float* d_enc_params; float* d_code;
-    float *d_wit_clear, *d_wit_min; int* d_wit_pair; unsigned* d_wit_count;      // the pair witness (jb_pair_witness / JB_FLAG_PAIR_WITNESS), allocated at first use
+    Dev<float> d_terms, d_enc_params, d_code;
+    struct Witness { Dev<float> clear, min; Dev<int> pair; Dev<unsigned> count; } wit;      // the pair witness (jb_pair_witness / JB_FLAG_PAIR_WITNESS), allocated at first use
 };
+static_assert(!std::is_copy_constructible<jb_handle>::value && !std::is_copy_assignable<jb_handle>::value, "the handle owns its memory: never copied");
 
 // ---------------------------------------------------------------------------------------------- RCCL, bound at run time
 // The library has no link-time dependency on RCCL: a host that never calls jb_comm_* never loads it, and a process that already
@@ -841,31 +854,27 @@ struct HipDeviceApi {
 
 static dim3 grid_lanes(int n) { return dim3((unsigned)(((size_t)n * 4 + 63) / 64)); }
 
-static int ensure_model_buffer(jb_handle* h, int n_tables) {
-    if ((size_t)n_tables != h->model_tables) {
-        if (h->d_model) JB_HIP(hipFree(h->d_model));
-        h->d_model = nullptr; h->model_tables = 0;
-        JB_HIP(hipMalloc(&h->d_model, (size_t)n_tables * LM_TABLE * sizeof(float)));
-        h->model_tables = n_tables;
-    }
-    return JB_OK;
-}
 // Which step kernel a handle runs.  JB_FLAG_LEAN is honoured where a LEAN instantiation exists: a shared model without the pair contact
 // (envs per wave 1, 2 or 4), or one model per env at four envs per wave (LEAN + PAIR, split tables).  Anything else that asks for LEAN is
 // refused (JB_E_INVALID) at the call that creates the combination - never silently run as the ordinary kernel.
-static int kernel_variant(const jb_handle* h) {
-    const bool lean_pair = h->ka.lean && h->ka.pair && h->ka.per_env_model && h->ka.epw == 4;
-    if (lean_pair) return JB_VARIANT_LEAN_PAIR;
-    if (h->ka.pair) return JB_VARIANT_PAIR;
-    if (h->ka.lean) return JB_VARIANT_LEAN;
+static int kernel_variant(const KArgs& k) {
+    if (k.lean && k.pair && k.per_env_model && k.epw == 4) return JB_VARIANT_LEAN_PAIR;
+    if (k.pair) return JB_VARIANT_PAIR;
+    if (k.lean) return JB_VARIANT_LEAN;
     return JB_VARIANT_ORDINARY;
 }
-static int check_variant(const jb_handle* h) {
-    if (h->ka.lean && h->ka.pair && !(h->ka.per_env_model && h->ka.epw == 4))
+static int check_variant(int lean, int pair, int per_env_model, int epw) {
+    if (lean && pair && !(per_env_model && epw == 4))
         return fail(JB_E_INVALID, "JB_FLAG_LEAN cannot be honoured: the pair-contact kernel has a two-waves-per-SIMD form only for one model per env at 4 envs per wave "
-                                  "(this handle: " + std::string(h->ka.per_env_model ? "one model per env" : "a shared model that needs the pair contact") + ", " + std::to_string(h->ka.epw) +
+                                  "(this handle: " + std::string(per_env_model ? "one model per env" : "a shared model that needs the pair contact") + ", " + std::to_string(epw) +
                                   " envs per wave); drop JB_FLAG_LEAN, or add JB_FLAG_NO_PAIR for floor contacts only");
     return JB_OK;
+}
+// The one way a model becomes the handle's (jb_create, jb_set_model_params, jb_randomise_models): `fresh`, when not empty, replaces the
+// table buffer (empty: the tables were rewritten in place), and the kernel arguments follow.  The caller has synchronised the stream.
+static void install_model(jb_handle* h, Dev<float> fresh, int per_env_model, int pair) {
+    if (fresh) h->d_model = std::move(fresh);
+    h->ka.lane_model = h->d_model.get(); h->ka.per_env_model = per_env_model; h->ka.pair = pair;
 }
 static int upload_model(jb_handle* h, const double* params, int n_tables) {
     std::vector<float> host((size_t)n_tables * LM_TABLE);
@@ -875,18 +884,14 @@ static int upload_model(jb_handle* h, const double* params, int n_tables) {
     }
     // which step kernel: the PAIR variant whenever the model(s) may bring the mass against a leg (see JB_FLAG_PAIR)
     const int pair = (h->cfg.flags & JB_FLAG_NO_PAIR) ? 0 : ((h->cfg.flags & JB_FLAG_PAIR) || n_tables > 1 || !mass_sweep_clear(params, 5e-4)) ? 1 : 0;
-    {   // a model that JB_FLAG_LEAN cannot run is refused BEFORE anything changes (the handle keeps the model it had)
-        jb_handle probe = *h;
-        probe.ka.pair = pair; probe.ka.per_env_model = n_tables > 1 ? 1 : 0;
-        int rc = check_variant(&probe);
-        if (rc) return rc;
-    }
-    { int rc = ensure_model_buffer(h, n_tables); if (rc) return rc; }
-    JB_HIP(hipMemcpyAsync(h->d_model, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const int per_env_model = n_tables > 1 ? 1 : 0;
+    // a model that JB_FLAG_LEAN cannot run is refused BEFORE anything changes (the handle keeps the model it had)
+    { int rc = check_variant(h->ka.lean, pair, per_env_model, h->ka.epw); if (rc) return rc; }
+    Dev<float> fresh;      // (a buffer of the same size is rewritten in place)
+    if (h->d_model.size() != host.size()) JB_HIP(fresh.alloc(host.size()));
+    JB_HIP(hipMemcpyAsync(fresh ? fresh.get() : h->d_model.get(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
-    h->ka.lane_model = h->d_model;
-    h->ka.per_env_model = n_tables > 1 ? 1 : 0;
-    h->ka.pair = pair;
+    install_model(h, std::move(fresh), per_env_model, pair);
     return JB_OK;
 }
 
@@ -921,34 +926,22 @@ static int create_impl(jb_handle* h) {      // every failure returns through jb_
     const size_t N = (size_t)cfg->n_envs;
     if (cfg->use_caller_stream) { h->stream = (hipStream_t)cfg->stream; h->own_stream = false; }
     else { JB_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    JB_HIP(hipMalloc(&h->d_root, sizeof(float) * ROOT_F * N));
-    JB_HIP(hipMalloc(&h->d_leg, sizeof(float) * LEG_F * 4 * N));
-    JB_HIP(hipMalloc(&h->d_step, sizeof(int) * N));
-    JB_HIP(hipMalloc(&h->d_episode, sizeof(unsigned) * N));
-    JB_HIP(hipMalloc(&h->d_action, sizeof(float) * N));
-    JB_HIP(hipMalloc(&h->d_obs, sizeof(float) * N * h->D));
-    JB_HIP(hipMalloc(&h->d_reward, sizeof(float) * N));
-    JB_HIP(hipMalloc(&h->d_done, N));
-    JB_HIP(hipMalloc(&h->d_mask, N));
-    JB_HIP(hipMalloc(&h->d_qpos, sizeof(double) * 16 * N));
-    JB_HIP(hipMalloc(&h->d_qvel, sizeof(double) * 15 * N));
-    JB_HIP(hipMalloc(&h->d_target, sizeof(double) * 3 * N));
-    JB_HIP(hipMalloc(&h->d_terms, sizeof(float) * 4 * N));
-    JB_HIP(hipMalloc(&h->d_resolve, sizeof(unsigned long long)));
+    JB_HIP(h->d_root.alloc(ROOT_F * N)); JB_HIP(h->d_leg.alloc(LEG_F * 4 * N)); JB_HIP(h->d_step.alloc(N)); JB_HIP(h->d_episode.alloc(N)); JB_HIP(h->d_resolve.alloc(1));
+    JB_HIP(h->d_action.alloc(N)); JB_HIP(h->d_obs.alloc(N * h->D)); JB_HIP(h->d_reward.alloc(N)); JB_HIP(h->d_done.alloc(N)); JB_HIP(h->d_mask.alloc(N));
+    JB_HIP(h->d_qpos.alloc(16 * N)); JB_HIP(h->d_qvel.alloc(15 * N)); JB_HIP(h->d_target.alloc(3 * N)); JB_HIP(h->d_terms.alloc(4 * N));
 #ifdef JB_CAPTURE
-    JB_HIP(hipMalloc(&h->d_capture, sizeof(float) * 64 * JB_CAPTURE_SLOTS));
-    JB_HIP(hipMalloc(&h->d_capture_count, sizeof(unsigned)));
-    JB_HIP(hipMemsetAsync(h->d_capture_count, 0, sizeof(unsigned), h->stream));
+    JB_HIP(h->d_capture.alloc(64 * JB_CAPTURE_SLOTS)); JB_HIP(h->d_capture_count.alloc(1));
+    JB_HIP(hipMemsetAsync(h->d_capture_count.get(), 0, sizeof(unsigned), h->stream));
 #endif
-    JB_HIP(hipMemsetAsync(h->d_resolve, 0, sizeof(unsigned long long), h->stream));
+    JB_HIP(hipMemsetAsync(h->d_resolve.get(), 0, sizeof(unsigned long long), h->stream));
 #ifdef JB_WAVE_STATS
-    JB_HIP(hipMalloc(&h->d_wave_stats, sizeof(unsigned long long) * (size_t)(16 + 64) * N));
-    JB_HIP(hipMemset(h->d_wave_stats, 0, sizeof(unsigned long long) * (size_t)(16 + 64) * N));
+    JB_HIP(h->d_wave_stats.alloc((size_t)(16 + 64) * N));
+    JB_HIP(hipMemset(h->d_wave_stats.get(), 0, sizeof(unsigned long long) * (size_t)(16 + 64) * N));
 #endif
-    JB_HIP(hipMemsetAsync(h->d_root, 0, sizeof(float) * ROOT_F * N, h->stream));
-    JB_HIP(hipMemsetAsync(h->d_leg, 0, sizeof(float) * LEG_F * 4 * N, h->stream));
-    JB_HIP(hipMemsetAsync(h->d_step, 0, sizeof(int) * N, h->stream));
-    JB_HIP(hipMemsetAsync(h->d_episode, 0, sizeof(unsigned) * N, h->stream));
+    JB_HIP(hipMemsetAsync(h->d_root.get(), 0, sizeof(float) * ROOT_F * N, h->stream));
+    JB_HIP(hipMemsetAsync(h->d_leg.get(), 0, sizeof(float) * LEG_F * 4 * N, h->stream));
+    JB_HIP(hipMemsetAsync(h->d_step.get(), 0, sizeof(int) * N, h->stream));
+    JB_HIP(hipMemsetAsync(h->d_episode.get(), 0, sizeof(unsigned) * N, h->stream));
     KArgs& k = h->ka;
     k.n = cfg->n_envs; k.task = cfg->task_id; k.substeps = cfg->substeps; k.step_limit = cfg->step_limit; k.auto_reset = cfg->auto_reset;
     k.contacts = cfg->contacts; k.max_newton = h->cfg.max_newton; k.random_pose = cfg->random_pose; k.per_env_model = 0;
@@ -971,22 +964,22 @@ static int create_impl(jb_handle* h) {      // every failure returns through jb_
         if (k.lean) { if (cfg->envs_per_wave <= 0) epw = 4; if (epw > 4) epw = 4; }     // LEAN: 4 envs per wave, 20 KB of LDS each: 8 waves per CU, two per SIMD
         k.epw = epw;
     }
-    k.root = h->d_root; k.leg = h->d_leg; k.step_count = h->d_step; k.episode = h->d_episode; k.wave_stats = h->d_wave_stats; k.resolve_count = h->d_resolve; k.capture = h->d_capture; k.capture_count = h->d_capture_count;
+    k.root = h->d_root.get(); k.leg = h->d_leg.get(); k.step_count = h->d_step.get(); k.episode = h->d_episode.get(); k.wave_stats = h->d_wave_stats.get();
+    k.resolve_count = h->d_resolve.get(); k.capture = h->d_capture.get(); k.capture_count = h->d_capture_count.get();
     {   // the step kernels read part of their arguments through the kernarg segment: make sure that layout is what they assume (once per
         // process; handles created from several threads at once are serialised here)
         static std::mutex probe_mutex;
         static bool probed = false;
         std::lock_guard<std::mutex> lock(probe_mutex);
         if (!probed) {
-            int* d_ok = nullptr;
-            JB_HIP(hipMalloc(&d_ok, sizeof(int)));
+            Dev<int> d_ok;
+            JB_HIP(d_ok.alloc(1));
             KArgs pa = KArgs(); StepIO pio = StepIO();
             pa.n = 0x1234567; pa.seed = 0x0123456789ABCDEFull; pa.root = (float*)0x10002000; pa.step_limit = 777;
             pio.n_steps = 4242; pio.obs_out = (float*)0x30004000; pio.every_step = 5; pio.wave_clock = (unsigned long long*)0x50006000; pio.pp.angle_threshold = 0.625f;
-            hipLaunchKernelGGL(jb_kernarg_probe_kernel, dim3(1), dim3(1), 0, h->stream, pa, pio, d_ok);
+            hipLaunchKernelGGL(jb_kernarg_probe_kernel, dim3(1), dim3(1), 0, h->stream, pa, pio, d_ok.get());
             int ok = 0;
-            const hipError_t e1 = hipGetLastError(), e2 = hipMemcpyAsync(&ok, d_ok, sizeof(int), hipMemcpyDeviceToHost, h->stream), e3 = hipStreamSynchronize(h->stream);
-            hipFree(d_ok);          // (on every path: nothing below returns before this)
+            const hipError_t e1 = hipGetLastError(), e2 = hipMemcpyAsync(&ok, d_ok.get(), sizeof(int), hipMemcpyDeviceToHost, h->stream), e3 = hipStreamSynchronize(h->stream);
             if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(JB_E_HIP, "kernarg probe failed to run");
             if (!ok) return fail(JB_E_HIP, "the step kernels' view of the kernarg segment does not match their arguments (compiler ABI change?): rebuild is needed with the layout fixed");
             probed = true;
@@ -1011,15 +1004,14 @@ int jb_create(const jb_config* cfg, jb_handle** out) {
     if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(JB_E_INVALID, "device_id out of range");
     jb::DeviceGuard<HipDeviceApi> guard;              // the caller's current device is restored on every return path
     if (guard.enter(cfg->device_id) != 0) return fail(JB_E_HIP, "hipSetDevice(" + std::to_string(cfg->device_id) + ") failed");
-    jb_handle* h = new (std::nothrow) jb_handle();
+    jb_handle* h = new (std::nothrow) jb_handle();      // (value-initialised: every plain member zero, every owner empty)
     if (!h) return fail(JB_E_INVALID, "out of host memory");
-    std::memset(h, 0, sizeof *h);
     h->cfg = *cfg;
     if (h->cfg.max_newton <= 0) h->cfg.max_newton = JB_DEFAULT_MAX_NEWTON;
     h->D = obs_dim(cfg->task_id);
     h->policy = default_policy_params<float>();
     const int rc = create_impl(h);
-    if (rc) {                               // one cleanup path: stream, every buffer allocated so far, the handle (keep the message)
+    if (rc) {                               // one cleanup path: the handle with what it holds so far, the stream (keep the message)
         const std::string msg = g_err;
         jb_destroy(h);
         g_err = msg;
@@ -1035,23 +1027,16 @@ int jb_destroy(jb_handle* h) {
     guard.enter(h->cfg.device_id);
     if (h->stream || !h->own_stream) hipStreamSynchronize(h->stream);
     if (h->comm && g_rccl.CommDestroy) { hipDeviceSynchronize(); g_rccl.CommDestroy(h->comm); h->comm = nullptr; }      // (device-wide: exchanges may be queued on streams of the caller's)
-    void* bufs[] = {h->d_tape, h->d_rows_stage, h->d_rew_stage, h->d_capture, h->d_capture_count, h->d_resolve, h->d_wave_order, h->d_wave_clock, h->d_ovc, h->d_terms, h->d_spec, h->d_root, h->d_leg, h->d_model, h->d_step, h->d_episode, h->d_action, h->d_obs, h->d_reward, h->d_done, h->d_mask, h->d_qpos, h->d_qvel, h->d_target, h->d_wave_stats, h->d_enc_params, h->d_code, h->d_wit_clear, h->d_wit_min, h->d_wit_pair, h->d_wit_count};
-    for (void* b : bufs) if (b) hipFree(b);
-    void* pinned[] = {h->p_action, h->p_obs, h->p_reward, h->p_done};
-    for (void* b : pinned) if (b) hipHostFree(b);
-    if (h->async_done) hipEventDestroy(h->async_done);
-    if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    const hipStream_t stream = h->own_stream ? h->stream : nullptr;      // (a caller's stream is never destroyed)
+    delete h;                                  // every buffer, the pinned staging and the event
+    if (stream) hipStreamDestroy(stream);
     return JB_OK;
 }
 
 int jb_set_obs_encoder(jb_handle* h, int32_t n_layers, const int32_t* dims, const int32_t* acts, const float* weights, const float* biases, int32_t vae) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
-    if (h->d_enc_params) { hipFree(h->d_enc_params); h->d_enc_params = nullptr; }
-    if (h->d_code) { hipFree(h->d_code); h->d_code = nullptr; }
-    h->enc = EncArgs();
-    if (n_layers == 0) return JB_OK;
+    if (n_layers == 0) { h->d_enc_params.reset(); h->d_code.reset(); h->enc = EncArgs(); return JB_OK; }
     if (n_layers < 0 || n_layers > JB_ENC_MAX_LAYERS || !dims || !acts || !weights || !biases) return fail(JB_E_INVALID, "encoder: 1.." + std::to_string(JB_ENC_MAX_LAYERS) + " layers with dims/acts/weights/biases");
     if (dims[0] != h->D) return fail(JB_E_INVALID, "encoder: dims[0] must be the observation width " + std::to_string(h->D));
     size_t nw = 0, nb = 0;
@@ -1070,13 +1055,12 @@ int jb_set_obs_encoder(jb_handle* h, int32_t n_layers, const int32_t* dims, cons
     }
     e.dims[n_layers] = dims[n_layers];
     e.seed = h->cfg.seed; e.env_offset = h->cfg.env_offset; e.call = 0;
-    std::vector<float> host(nw + nb);
-    std::copy(weights, weights + nw, host.begin());
-    std::copy(biases, biases + nb, host.begin() + nw);
-    JB_HIP(hipMalloc(&h->d_enc_params, host.size() * sizeof(float)));
-    JB_HIP(hipMalloc(&h->d_code, sizeof(float) * (size_t)e.n * e.out_dim));
-    JB_HIP(hipMemcpy(h->d_enc_params, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-    e.params = h->d_enc_params;
+    Dev<float> params, code;          // the handle keeps the encoder it had until every step below has succeeded
+    JB_HIP(params.alloc(nw + nb)); JB_HIP(code.alloc((size_t)e.n * e.out_dim));
+    JB_HIP(hipMemcpy(params.get(), weights, nw * sizeof(float), hipMemcpyHostToDevice));
+    JB_HIP(hipMemcpy(params.get() + nw, biases, nb * sizeof(float), hipMemcpyHostToDevice));
+    e.params = params.get();
+    h->d_enc_params = std::move(params); h->d_code = std::move(code);
     h->enc = e;
     return JB_OK;
 }
@@ -1096,10 +1080,10 @@ int jb_encode(jb_handle* h, const float* obs, float* code_out) {
     JB_ENTER(h);
     if (h->enc.n_layers <= 0) return fail(JB_E_INVALID, "no observation encoder set (jb_set_obs_encoder)");
     const size_t N = (size_t)h->cfg.n_envs;
-    JB_HIP(hipMemcpyAsync(h->d_obs, obs, sizeof(float) * N * h->D, hipMemcpyHostToDevice, h->stream));
-    int rc = jb_encode_device(h, h->d_obs, h->d_code);
+    JB_HIP(hipMemcpyAsync(h->d_obs.get(), obs, sizeof(float) * N * h->D, hipMemcpyHostToDevice, h->stream));
+    int rc = jb_encode_device(h, h->d_obs.get(), h->d_code.get());
     if (rc) return rc;
-    JB_HIP(hipMemcpyAsync(code_out, h->d_code, sizeof(float) * N * h->enc.out_dim, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipMemcpyAsync(code_out, h->d_code.get(), sizeof(float) * N * h->enc.out_dim, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
@@ -1128,16 +1112,15 @@ int jb_reset_device(jb_handle* h, const uint8_t* d_mask, float* d_obs_out) {
     return JB_OK;
 }
 static int ensure_witness(jb_handle* h) {
-    if (h->d_wit_clear) return JB_OK;
+    if (h->wit.clear) return JB_OK;
     const size_t N = (size_t)h->cfg.n_envs;
-    JB_HIP(hipMalloc(&h->d_wit_clear, sizeof(float) * N));
-    JB_HIP(hipMalloc(&h->d_wit_min, sizeof(float) * N));
-    JB_HIP(hipMalloc(&h->d_wit_pair, sizeof(int) * 2 * N));
-    JB_HIP(hipMalloc(&h->d_wit_count, sizeof(unsigned) * N));
+    jb_handle::Witness w;          // all or nothing: the handle takes the group once every buffer is allocated and initialised
+    JB_HIP(w.clear.alloc(N)); JB_HIP(w.min.alloc(N)); JB_HIP(w.pair.alloc(2 * N)); JB_HIP(w.count.alloc(N));
     std::vector<float> inf(N, INFINITY);
-    JB_HIP(hipMemcpyAsync(h->d_wit_min, inf.data(), sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
-    JB_HIP(hipMemsetAsync(h->d_wit_count, 0, sizeof(unsigned) * N, h->stream));
+    JB_HIP(hipMemcpyAsync(w.min.get(), inf.data(), sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
+    JB_HIP(hipMemsetAsync(w.count.get(), 0, sizeof(unsigned) * N, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));          // (`inf` goes out of scope)
+    h->wit = std::move(w);
     return JB_OK;
 }
 static int launch_step(jb_handle* h, StepIO io, int packed_rows) {
@@ -1145,17 +1128,19 @@ static int launch_step(jb_handle* h, StepIO io, int packed_rows) {
     if (io.n_steps < 1) return fail(JB_E_INVALID, "n_steps must be >= 1");
     if (!io.use_policy && !io.actions) return fail(JB_E_INVALID, "action buffer is NULL");
     JB_ENTER(h);
-    { int rc = check_variant(h); if (rc) return rc; }
+    { int rc = check_variant(h->ka.lean, h->ka.pair, h->ka.per_env_model, h->ka.epw); if (rc) return rc; }
     RoctxRange range(io.n_steps > 1 ? "jb_step_many" : "jb_step");
     h->ka.packed_rows = packed_rows;
     io.pp = h->policy;
     const dim3 grid((unsigned)((h->cfg.n_envs + h->ka.epw - 1) / h->ka.epw));
     if (!h->d_wave_clock) {
-        JB_HIP(hipMalloc(&h->d_wave_clock, sizeof(unsigned long long) * (size_t)h->cfg.n_envs));      // (>= the number of waves for any envs-per-wave)
-        JB_HIP(hipMemsetAsync(h->d_wave_clock, 0, sizeof(unsigned long long) * (size_t)h->cfg.n_envs, h->stream));
+        Dev<unsigned long long> clock;
+        JB_HIP(clock.alloc((size_t)h->cfg.n_envs));      // (>= the number of waves for any envs-per-wave)
+        JB_HIP(hipMemsetAsync(clock.get(), 0, sizeof(unsigned long long) * (size_t)h->cfg.n_envs, h->stream));
+        h->d_wave_clock = std::move(clock);
     }
-    io.wave_clock = h->d_wave_clock;
-    const int variant = kernel_variant(h);
+    io.wave_clock = h->d_wave_clock.get();
+    const int variant = kernel_variant(h->ka);
     // more waves than the device holds at once -> launch them longest first (the order comes from the previous launch's clocks)
     bool reorder = false;
     int fold_from = 0;
@@ -1170,12 +1155,14 @@ static int launch_step(jb_handle* h, StepIO io, int packed_rows) {
         // two waves per SIMD and the whole batch resident: no launch ORDER to choose, but who shares a SIMD with whom (jb_wave_order_kernel)
         if (per_simd_x2 == 4 && (int)grid.x > h->wave_slots && !reorder) { reorder = true; fold_from = h->wave_slots; }
         if (reorder && !h->d_wave_order) {
-            JB_HIP(hipMalloc(&h->d_wave_order, sizeof(int) * (size_t)h->cfg.n_envs));
-            hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock, h->d_wave_order, (int)grid.x, fold_from);      // (clocks all zero: identity)
+            Dev<int> order;
+            JB_HIP(order.alloc((size_t)h->cfg.n_envs));
+            hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock.get(), order.get(), (int)grid.x, fold_from);      // (clocks all zero: identity)
             JB_HIP(hipGetLastError());
+            h->d_wave_order = std::move(order);
         }
     }
-    io.wave_order = reorder ? h->d_wave_order : nullptr;
+    io.wave_order = reorder ? h->d_wave_order.get() : nullptr;
     const bool lean_pair = variant == JB_VARIANT_LEAN_PAIR, use_lean = lean_pair || variant == JB_VARIANT_LEAN;
     const bool aux_bodies = variant == JB_VARIANT_ORDINARY && h->ka.epw <= 4;      // (step_body: AUX - an aux block behind every staged table)
     const size_t lds_bytes = lean_pair ? ((size_t)SC_COUNT_LEAN_PAIR * 4 * h->ka.epw + (size_t)LM_SPLIT_RES * h->ka.epw) * sizeof(float)
@@ -1187,9 +1174,8 @@ static int launch_step(jb_handle* h, StepIO io, int packed_rows) {
     const size_t lds_bytes_x = lds_bytes;
 #endif
     if (use_lean && !h->d_ovc) {      // the LEAN variant's overflow candidates (beyond the row cache): one block per wave
-        const size_t waves = (size_t)grid.x, fl = waves * OVC_FLOATS_PER_LANE * 4 * h->ka.epw;
-        JB_HIP(hipMalloc(&h->d_ovc, fl * sizeof(float)));
-        h->ka.ovc_buf = h->d_ovc;
+        JB_HIP(h->d_ovc.alloc((size_t)grid.x * OVC_FLOATS_PER_LANE * 4 * h->ka.epw));      // (a failed allocation leaves it empty)
+        h->ka.ovc_buf = h->d_ovc.get();
     }
 #define JB_LAUNCH_STEP(E) hipLaunchKernelGGL(jb_step_kernel<E>, grid, dim3(64), lds_bytes_x, h->stream, h->ka, io)
 #define JB_LAUNCH_LEAN(E) hipLaunchKernelGGL(jb_step_kernel_lean<E>, grid, dim3(64), lds_bytes_x, h->stream, h->ka, io)
@@ -1227,18 +1213,18 @@ static int launch_step(jb_handle* h, StepIO io, int packed_rows) {
 #undef JB_LAUNCH_PAIR
     JB_HIP(hipGetLastError());
     if (reorder) {
-        hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock, h->d_wave_order, (int)grid.x, fold_from);
+        hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock.get(), h->d_wave_order.get(), (int)grid.x, fold_from);
         JB_HIP(hipGetLastError());
     }
     if (h->cfg.flags & JB_FLAG_PAIR_WITNESS) {      // one witness pass behind every step launch (the state the launch left)
         int rc = ensure_witness(h);
         if (rc) return rc;
-        hipLaunchKernelGGL(jb_witness_kernel, dim3((unsigned)((h->cfg.n_envs + 63) / 64)), dim3(64), 0, h->stream, h->ka, (float*)nullptr, (int*)nullptr, h->d_wit_min, h->d_wit_count);
+        hipLaunchKernelGGL(jb_witness_kernel, dim3((unsigned)((h->cfg.n_envs + 63) / 64)), dim3(64), 0, h->stream, h->ka, (float*)nullptr, (int*)nullptr, h->wit.min.get(), h->wit.count.get());
         JB_HIP(hipGetLastError());
     }
     return JB_OK;
 }
-int jb_kernel_variant(jb_handle* h) { return h ? kernel_variant(h) : JB_E_INVALID; }
+int jb_kernel_variant(jb_handle* h) { return h ? kernel_variant(h->ka) : JB_E_INVALID; }
 int jb_envs_per_wave(jb_handle* h) { return h ? h->ka.epw : JB_E_INVALID; }
 int jb_step_device(jb_handle* h, const float* d_action, float* d_obs_out, float* d_reward_out, uint8_t* d_done_out) {
     if (!d_action) return fail(JB_E_INVALID, "handle/action is NULL");
@@ -1272,11 +1258,10 @@ int jb_step_many_device(jb_handle* h, int32_t n_steps, const float* d_actions, f
     return launch_step(h, io, 0);
 }
 // grow-only device staging owned by the handle: (re)allocated only when a call needs more than any call before it
-static int ensure_stage(jb_handle* h, float** buf, size_t* cap, size_t floats, const char* what) {
-    if (floats <= *cap) return JB_OK;
-    if (*buf) { JB_HIP(hipStreamSynchronize(h->stream)); JB_HIP(hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    if (hipMalloc(buf, sizeof(float) * floats) != hipSuccess) { *buf = nullptr; return fail(JB_E_HIP, std::string("out of device memory for ") + what); }
-    *cap = floats;
+static int ensure_stage(jb_handle* h, Dev<float>& buf, size_t floats, const char* what) {
+    if (floats <= buf.size()) return JB_OK;
+    if (buf) JB_HIP(hipStreamSynchronize(h->stream));      // (the buffer may still be in use by queued work)
+    if (buf.alloc(floats) != hipSuccess) return fail(JB_E_HIP, std::string("out of device memory for ") + what);
     return JB_OK;
 }
 // host-buffer form of jb_step_many_device: actions [K, N] (NULL: the in-kernel heuristic policy), rows_out [K, N, D+2] (nullable);
@@ -1289,13 +1274,13 @@ int jb_step_many(jb_handle* h, int32_t n_steps, const float* actions, float* row
     const size_t N = (size_t)h->cfg.n_envs, K = (size_t)n_steps, W = (size_t)h->D + 2;
     int rc = JB_OK;
     if (actions) {
-        rc = ensure_stage(h, &h->d_tape, &h->tape_cap, K * N, "the action tape");
+        rc = ensure_stage(h, h->d_tape, K * N, "the action tape");
         if (rc) return rc;
-        JB_HIP(hipMemcpyAsync(h->d_tape, actions, sizeof(float) * K * N, hipMemcpyHostToDevice, h->stream));
+        JB_HIP(hipMemcpyAsync(h->d_tape.get(), actions, sizeof(float) * K * N, hipMemcpyHostToDevice, h->stream));
     }
-    if (rows_out) { rc = ensure_stage(h, &h->d_rows_stage, &h->rows_cap, K * N * W, "the rows"); if (rc) return rc; }
-    rc = jb_step_many_device(h, n_steps, actions ? h->d_tape : nullptr, rows_out ? h->d_rows_stage : nullptr, nullptr, nullptr, nullptr);
-    if (!rc && rows_out && hipMemcpyAsync(rows_out, h->d_rows_stage, sizeof(float) * K * N * W, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "jb_step_many: copy of the rows failed");
+    if (rows_out) { rc = ensure_stage(h, h->d_rows_stage, K * N * W, "the rows"); if (rc) return rc; }
+    rc = jb_step_many_device(h, n_steps, actions ? h->d_tape.get() : nullptr, rows_out ? h->d_rows_stage.get() : nullptr, nullptr, nullptr, nullptr);
+    if (!rc && rows_out && hipMemcpyAsync(rows_out, h->d_rows_stage.get(), sizeof(float) * K * N * W, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "jb_step_many: copy of the rows failed");
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (!rc && e != hipSuccess) rc = fail(JB_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return rc;
@@ -1303,9 +1288,7 @@ int jb_step_many(jb_handle* h, int32_t n_steps, const float* actions, float* row
 int jb_release_staging(jb_handle* h) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
-    float** bufs[] = {&h->d_tape, &h->d_rows_stage, &h->d_rew_stage};
-    size_t* caps[] = {&h->tape_cap, &h->rows_cap, &h->rew_cap};
-    for (int i = 0; i < 3; i++) { if (*bufs[i]) hipFree(*bufs[i]); *bufs[i] = nullptr; *caps[i] = 0; }
+    h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset();
     return JB_OK;
 }
 // how long each wave of the last step launch lived, in seconds (s_memrealtime, 100 MHz): out[0 .. n_waves); returns the number of waves
@@ -1316,7 +1299,7 @@ int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves) {
     if (!h->d_wave_clock) return fail(JB_E_INVALID, "no step has been launched yet");
     JB_HIP(hipStreamSynchronize(h->stream));
     std::vector<unsigned long long> t((size_t)waves);
-    JB_HIP(hipMemcpy(t.data(), h->d_wave_clock, sizeof(unsigned long long) * (size_t)waves, hipMemcpyDeviceToHost));
+    JB_HIP(hipMemcpy(t.data(), h->d_wave_clock.get(), sizeof(unsigned long long) * (size_t)waves, hipMemcpyDeviceToHost));
     for (int i = 0; i < waves && i < max_waves; i++) out[i] = (double)t[(size_t)i] * 1e-8;
     return waves;
 }
@@ -1331,10 +1314,10 @@ int jb_reset(jb_handle* h, const uint8_t* mask, float* obs_out) {
     JB_ENTER(h);
     if (h->async_pending) return fail(JB_E_INVALID, "jb_reset: a jb_step_async is pending (jb_step_wait first)");
     const size_t N = (size_t)h->cfg.n_envs;
-    if (mask) JB_HIP(hipMemcpyAsync(h->d_mask, mask, N, hipMemcpyHostToDevice, h->stream));
-    int rc = jb_reset_device(h, mask ? h->d_mask : nullptr, obs_out ? h->d_obs : nullptr);
+    if (mask) JB_HIP(hipMemcpyAsync(h->d_mask.get(), mask, N, hipMemcpyHostToDevice, h->stream));
+    int rc = jb_reset_device(h, mask ? h->d_mask.get() : nullptr, obs_out ? h->d_obs.get() : nullptr);
     if (rc) return rc;
-    if (obs_out) JB_HIP(hipMemcpyAsync(obs_out, h->d_obs, sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
+    if (obs_out) JB_HIP(hipMemcpyAsync(obs_out, h->d_obs.get(), sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
@@ -1344,12 +1327,12 @@ int jb_step(jb_handle* h, const float* action, float* obs_out, float* reward_out
     if (h->async_pending) return fail(JB_E_INVALID, "jb_step: a jb_step_async is pending (jb_step_wait first)");
     RoctxRange range("jb_step_host_buffers");
     const size_t N = (size_t)h->cfg.n_envs;
-    JB_HIP(hipMemcpyAsync(h->d_action, action, sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
-    int rc = jb_step_device(h, h->d_action, h->d_obs, h->d_reward, h->d_done);
+    JB_HIP(hipMemcpyAsync(h->d_action.get(), action, sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
+    int rc = jb_step_device(h, h->d_action.get(), h->d_obs.get(), h->d_reward.get(), h->d_done.get());
     if (rc) return rc;
-    if (obs_out) JB_HIP(hipMemcpyAsync(obs_out, h->d_obs, sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
-    if (reward_out) JB_HIP(hipMemcpyAsync(reward_out, h->d_reward, sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
-    if (done_out) JB_HIP(hipMemcpyAsync(done_out, h->d_done, N, hipMemcpyDeviceToHost, h->stream));
+    if (obs_out) JB_HIP(hipMemcpyAsync(obs_out, h->d_obs.get(), sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
+    if (reward_out) JB_HIP(hipMemcpyAsync(reward_out, h->d_reward.get(), sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
+    if (done_out) JB_HIP(hipMemcpyAsync(done_out, h->d_done.get(), N, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
@@ -1360,22 +1343,22 @@ int jb_step_async(jb_handle* h, const float* action) {
     JB_ENTER(h);
     if (h->async_pending) return fail(JB_E_INVALID, "jb_step_async: the previous step has not been waited for (jb_step_wait)");
     const size_t N = (size_t)h->cfg.n_envs;
-    if (!h->p_action) {
-        JB_HIP(hipHostMalloc((void**)&h->p_action, sizeof(float) * N, hipHostMallocDefault));
-        JB_HIP(hipHostMalloc((void**)&h->p_obs, sizeof(float) * N * h->D, hipHostMallocDefault));
-        JB_HIP(hipHostMalloc((void**)&h->p_reward, sizeof(float) * N, hipHostMallocDefault));
-        JB_HIP(hipHostMalloc((void**)&h->p_done, N, hipHostMallocDefault));
-        JB_HIP(hipEventCreateWithFlags(&h->async_done, hipEventDisableTiming));
+    jb_handle::AsyncStage& a = h->async;
+    if (!a.copied) {          // all or nothing: the handle takes the staging once every buffer and the event exist
+        jb_handle::AsyncStage fresh;
+        JB_HIP(fresh.action.alloc(N)); JB_HIP(fresh.obs.alloc(N * h->D)); JB_HIP(fresh.reward.alloc(N)); JB_HIP(fresh.done.alloc(N));
+        JB_HIP(fresh.copied.alloc(1));
+        a = std::move(fresh);
     }
     RoctxRange range("jb_step_async");
-    std::memcpy(h->p_action, action, sizeof(float) * N);
-    JB_HIP(hipMemcpyAsync(h->d_action, h->p_action, sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
-    int rc = jb_step_device(h, h->d_action, h->d_obs, h->d_reward, h->d_done);
+    std::memcpy(a.action.get(), action, sizeof(float) * N);
+    JB_HIP(hipMemcpyAsync(h->d_action.get(), a.action.get(), sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
+    int rc = jb_step_device(h, h->d_action.get(), h->d_obs.get(), h->d_reward.get(), h->d_done.get());
     if (rc) return rc;
-    JB_HIP(hipMemcpyAsync(h->p_obs, h->d_obs, sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
-    JB_HIP(hipMemcpyAsync(h->p_reward, h->d_reward, sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
-    JB_HIP(hipMemcpyAsync(h->p_done, h->d_done, N, hipMemcpyDeviceToHost, h->stream));
-    JB_HIP(hipEventRecord(h->async_done, h->stream));
+    JB_HIP(hipMemcpyAsync(a.obs.get(), h->d_obs.get(), sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipMemcpyAsync(a.reward.get(), h->d_reward.get(), sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipMemcpyAsync(a.done.get(), h->d_done.get(), N, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipEventRecord(a.copied.get(), h->stream));
     h->async_pending = true;
     return JB_OK;
 }
@@ -1384,29 +1367,29 @@ int jb_step_wait(jb_handle* h, float* obs_out, float* reward_out, uint8_t* done_
     if (!h->async_pending) return fail(JB_E_INVALID, "jb_step_wait: no jb_step_async is pending");
     JB_ENTER(h);
     h->async_pending = false;          // (whatever happens below, the pairing async -> wait is used up)
-    JB_HIP(hipEventSynchronize(h->async_done));
+    JB_HIP(hipEventSynchronize(h->async.copied.get()));
     const size_t N = (size_t)h->cfg.n_envs;
-    if (obs_out) std::memcpy(obs_out, h->p_obs, sizeof(float) * N * h->D);
-    if (reward_out) std::memcpy(reward_out, h->p_reward, sizeof(float) * N);
-    if (done_out) std::memcpy(done_out, h->p_done, N);
+    if (obs_out) std::memcpy(obs_out, h->async.obs.get(), sizeof(float) * N * h->D);
+    if (reward_out) std::memcpy(reward_out, h->async.reward.get(), sizeof(float) * N);
+    if (done_out) std::memcpy(done_out, h->async.done.get(), N);
     return JB_OK;
 }
 int jb_step_views(jb_handle* h, const float** obs, const float** reward, const uint8_t** done) {
     if (!h) return fail(JB_E_INVALID, "handle is NULL");
-    if (!h->p_action) return fail(JB_E_INVALID, "jb_step_views: no jb_step_async yet (the pinned buffers come into being with the first one)");
-    if (obs) *obs = h->p_obs;
-    if (reward) *reward = h->p_reward;
-    if (done) *done = h->p_done;
+    if (!h->async.copied) return fail(JB_E_INVALID, "jb_step_views: no jb_step_async yet (the pinned buffers come into being with the first one)");
+    if (obs) *obs = h->async.obs.get();
+    if (reward) *reward = h->async.reward.get();
+    if (done) *done = h->async.done.get();
     return JB_OK;
 }
 int jb_observe(jb_handle* h, float* obs_out, float* reward_out) {
     if (!h || !obs_out) return fail(JB_E_INVALID, "handle/obs_out is NULL");
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
-    int rc = jb_observe_device(h, h->d_obs, reward_out ? h->d_reward : nullptr);
+    int rc = jb_observe_device(h, h->d_obs.get(), reward_out ? h->d_reward.get() : nullptr);
     if (rc) return rc;
-    JB_HIP(hipMemcpyAsync(obs_out, h->d_obs, sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
-    if (reward_out) JB_HIP(hipMemcpyAsync(reward_out, h->d_reward, sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipMemcpyAsync(obs_out, h->d_obs.get(), sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream));
+    if (reward_out) JB_HIP(hipMemcpyAsync(reward_out, h->d_reward.get(), sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
@@ -1428,8 +1411,8 @@ int jb_rollout_policy_device(jb_handle* h, int32_t n_steps, float* d_obs_inout /
     StepIO io = StepIO();
     io.n_steps = n_steps; io.use_policy = 1; io.obs_in = d_obs_inout;
     io.obs_out = d_obs_inout;
-    io.reward_out = d_rewards ? d_rewards : h->d_reward; io.every_step = d_rewards ? 2 : 0;
-    io.done_out = d_done_last ? d_done_last : h->d_done;
+    io.reward_out = d_rewards ? d_rewards : h->d_reward.get(); io.every_step = d_rewards ? 2 : 0;
+    io.done_out = d_done_last ? d_done_last : h->d_done.get();
     return launch_step(h, io, 0);
 }
 int jb_rollout_policy(jb_handle* h, int32_t n_steps, float* rewards_out /*[K,N] host, nullable*/, float* obs_out /*[N,D] host, nullable*/) {
@@ -1437,11 +1420,11 @@ int jb_rollout_policy(jb_handle* h, int32_t n_steps, float* rewards_out /*[K,N] 
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
     const bool want_rew = rewards_out && n_steps > 0;
-    if (want_rew) { int rc0 = ensure_stage(h, &h->d_rew_stage, &h->rew_cap, N * (size_t)n_steps, "the rewards"); if (rc0) return rc0; }
-    int rc = jb_observe_device(h, h->d_obs, nullptr);
-    if (!rc) rc = jb_rollout_policy_device(h, n_steps, h->d_obs, want_rew ? h->d_rew_stage : nullptr, nullptr);
-    if (!rc && want_rew && hipMemcpyAsync(rewards_out, h->d_rew_stage, sizeof(float) * N * (size_t)n_steps, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "copy of rewards failed");
-    if (!rc && obs_out && hipMemcpyAsync(obs_out, h->d_obs, sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "copy of observations failed");
+    if (want_rew) { int rc0 = ensure_stage(h, h->d_rew_stage, N * (size_t)n_steps, "the rewards"); if (rc0) return rc0; }
+    int rc = jb_observe_device(h, h->d_obs.get(), nullptr);
+    if (!rc) rc = jb_rollout_policy_device(h, n_steps, h->d_obs.get(), want_rew ? h->d_rew_stage.get() : nullptr, nullptr);
+    if (!rc && want_rew && hipMemcpyAsync(rewards_out, h->d_rew_stage.get(), sizeof(float) * N * (size_t)n_steps, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "copy of rewards failed");
+    if (!rc && obs_out && hipMemcpyAsync(obs_out, h->d_obs.get(), sizeof(float) * N * h->D, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "copy of observations failed");
     hipError_t e = hipStreamSynchronize(h->stream);
     if (!rc && e != hipSuccess) rc = fail(JB_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return rc;
@@ -1450,10 +1433,10 @@ int jb_policy(jb_handle* h, const float* obs, float* action) {
     if (!h || !obs || !action) return fail(JB_E_INVALID, "handle/obs/action is NULL");
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
-    JB_HIP(hipMemcpyAsync(h->d_obs, obs, sizeof(float) * N * h->D, hipMemcpyHostToDevice, h->stream));
-    int rc = jb_policy_device(h, h->d_obs, h->d_action);
+    JB_HIP(hipMemcpyAsync(h->d_obs.get(), obs, sizeof(float) * N * h->D, hipMemcpyHostToDevice, h->stream));
+    int rc = jb_policy_device(h, h->d_obs.get(), h->d_action.get());
     if (rc) return rc;
-    JB_HIP(hipMemcpyAsync(action, h->d_action, sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipMemcpyAsync(action, h->d_action.get(), sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
@@ -1473,32 +1456,32 @@ int jb_reward_terms_device(jb_handle* h, float* d_terms_out) {
 int jb_reward_terms(jb_handle* h, float* terms_out) {
     if (!h || !terms_out) return fail(JB_E_INVALID, "handle/terms is NULL");
     JB_ENTER(h);
-    int rc = jb_reward_terms_device(h, h->d_terms);
+    int rc = jb_reward_terms_device(h, h->d_terms.get());
     if (rc) return rc;
-    JB_HIP(hipMemcpyAsync(terms_out, h->d_terms, sizeof(float) * 4 * (size_t)h->cfg.n_envs, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipMemcpyAsync(terms_out, h->d_terms.get(), sizeof(float) * 4 * (size_t)h->cfg.n_envs, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
 int jb_get_state(jb_handle* h, double* qpos, double* qvel, double* target) {
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
-    hipLaunchKernelGGL(jb_export_kernel, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, h->stream, h->ka, qpos ? h->d_qpos : nullptr, qvel ? h->d_qvel : nullptr,
-                       target ? h->d_target : nullptr);
+    hipLaunchKernelGGL(jb_export_kernel, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, h->stream, h->ka, qpos ? h->d_qpos.get() : nullptr, qvel ? h->d_qvel.get() : nullptr,
+                       target ? h->d_target.get() : nullptr);
     JB_HIP(hipGetLastError());
-    if (qpos) JB_HIP(hipMemcpyAsync(qpos, h->d_qpos, sizeof(double) * 16 * N, hipMemcpyDeviceToHost, h->stream));
-    if (qvel) JB_HIP(hipMemcpyAsync(qvel, h->d_qvel, sizeof(double) * 15 * N, hipMemcpyDeviceToHost, h->stream));
-    if (target) JB_HIP(hipMemcpyAsync(target, h->d_target, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, h->stream));
+    if (qpos) JB_HIP(hipMemcpyAsync(qpos, h->d_qpos.get(), sizeof(double) * 16 * N, hipMemcpyDeviceToHost, h->stream));
+    if (qvel) JB_HIP(hipMemcpyAsync(qvel, h->d_qvel.get(), sizeof(double) * 15 * N, hipMemcpyDeviceToHost, h->stream));
+    if (target) JB_HIP(hipMemcpyAsync(target, h->d_target.get(), sizeof(double) * 3 * N, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
 int jb_set_state(jb_handle* h, const double* qpos, const double* qvel, const double* target) {
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
-    if (qpos) JB_HIP(hipMemcpyAsync(h->d_qpos, qpos, sizeof(double) * 16 * N, hipMemcpyHostToDevice, h->stream));
-    if (qvel) JB_HIP(hipMemcpyAsync(h->d_qvel, qvel, sizeof(double) * 15 * N, hipMemcpyHostToDevice, h->stream));
-    if (target) JB_HIP(hipMemcpyAsync(h->d_target, target, sizeof(double) * 3 * N, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(jb_import_kernel, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, h->stream, h->ka, qpos ? h->d_qpos : nullptr, qvel ? h->d_qvel : nullptr,
-                       target ? h->d_target : nullptr);
+    if (qpos) JB_HIP(hipMemcpyAsync(h->d_qpos.get(), qpos, sizeof(double) * 16 * N, hipMemcpyHostToDevice, h->stream));
+    if (qvel) JB_HIP(hipMemcpyAsync(h->d_qvel.get(), qvel, sizeof(double) * 15 * N, hipMemcpyHostToDevice, h->stream));
+    if (target) JB_HIP(hipMemcpyAsync(h->d_target.get(), target, sizeof(double) * 3 * N, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(jb_import_kernel, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, h->stream, h->ka, qpos ? h->d_qpos.get() : nullptr, qvel ? h->d_qvel.get() : nullptr,
+                       target ? h->d_target.get() : nullptr);
     JB_HIP(hipGetLastError());
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
@@ -1507,9 +1490,9 @@ int jb_get_counters(jb_handle* h, int32_t* step_count, uint32_t* episode, float*
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
     JB_HIP(hipStreamSynchronize(h->stream));
-    if (step_count) JB_HIP(hipMemcpy(step_count, h->d_step, sizeof(int) * N, hipMemcpyDeviceToHost));
-    if (episode) JB_HIP(hipMemcpy(episode, h->d_episode, sizeof(unsigned) * N, hipMemcpyDeviceToHost));
-    if (solver_cap_hits) JB_HIP(hipMemcpy(solver_cap_hits, h->d_root + RF_FAIL * N, sizeof(float) * N, hipMemcpyDeviceToHost));
+    if (step_count) JB_HIP(hipMemcpy(step_count, h->d_step.get(), sizeof(int) * N, hipMemcpyDeviceToHost));
+    if (episode) JB_HIP(hipMemcpy(episode, h->d_episode.get(), sizeof(unsigned) * N, hipMemcpyDeviceToHost));
+    if (solver_cap_hits) JB_HIP(hipMemcpy(solver_cap_hits, h->d_root.get() + RF_FAIL * N, sizeof(float) * N, hipMemcpyDeviceToHost));
     return JB_OK;
 }
 // how often the contact solve needed its second, line-searched pass: wave-substeps since jb_create (jb_sim.hpp newton_phase<LS = true>)
@@ -1518,7 +1501,7 @@ int jb_solver_stats(jb_handle* h, uint64_t* resolved_wave_substeps) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
     unsigned long long v = 0;
-    JB_HIP(hipMemcpy(&v, h->d_resolve, sizeof v, hipMemcpyDeviceToHost));
+    JB_HIP(hipMemcpy(&v, h->d_resolve.get(), sizeof v, hipMemcpyDeviceToHost));
     *resolved_wave_substeps = (uint64_t)v;
     return JB_OK;
 }
@@ -1528,9 +1511,9 @@ int jb_debug_captured(jb_handle* h, float* out, int32_t max_records) {
     if (!h || !out) return fail(JB_E_INVALID, "NULL");
     JB_HIP(hipStreamSynchronize(h->stream));
     unsigned n = 0;
-    JB_HIP(hipMemcpy(&n, h->d_capture_count, sizeof n, hipMemcpyDeviceToHost));
+    JB_HIP(hipMemcpy(&n, h->d_capture_count.get(), sizeof n, hipMemcpyDeviceToHost));
     const int m = (int)n < max_records ? (int)n : max_records;
-    JB_HIP(hipMemcpy(out, h->d_capture, sizeof(float) * 64 * (size_t)(m < JB_CAPTURE_SLOTS ? m : JB_CAPTURE_SLOTS), hipMemcpyDeviceToHost));
+    JB_HIP(hipMemcpy(out, h->d_capture.get(), sizeof(float) * 64 * (size_t)(m < JB_CAPTURE_SLOTS ? m : JB_CAPTURE_SLOTS), hipMemcpyDeviceToHost));
     return (int)n;
 }
 #endif
@@ -1539,7 +1522,7 @@ int jb_debug_captured(jb_handle* h, float* out, int32_t max_records) {
 int jb_debug_wave_stats(jb_handle* h, unsigned long long* out, int32_t n_waves) {
     if (!h || !out) return fail(JB_E_INVALID, "NULL");
     JB_HIP(hipStreamSynchronize(h->stream));
-    JB_HIP(hipMemcpy(out, h->d_wave_stats, sizeof(unsigned long long) * 16 * n_waves, hipMemcpyDeviceToHost));
+    JB_HIP(hipMemcpy(out, h->d_wave_stats.get(), sizeof(unsigned long long) * 16 * n_waves, hipMemcpyDeviceToHost));
     return h->ka.epw;
 }
 #endif
@@ -1549,11 +1532,11 @@ int jb_pair_witness(jb_handle* h, float* clearance_out, int32_t* pairs_out, int3
     int rc = ensure_witness(h);
     if (rc) return rc;
     const size_t N = (size_t)h->cfg.n_envs;
-    hipLaunchKernelGGL(jb_witness_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, h->ka, h->d_wit_clear, h->d_wit_pair, (float*)nullptr, (unsigned*)nullptr);
+    hipLaunchKernelGGL(jb_witness_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, h->ka, h->wit.clear.get(), h->wit.pair.get(), (float*)nullptr, (unsigned*)nullptr);
     JB_HIP(hipGetLastError());
     std::vector<float> host(N);
-    JB_HIP(hipMemcpyAsync(host.data(), h->d_wit_clear, sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
-    if (pairs_out) JB_HIP(hipMemcpyAsync(pairs_out, h->d_wit_pair, sizeof(int) * 2 * N, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipMemcpyAsync(host.data(), h->wit.clear.get(), sizeof(float) * N, hipMemcpyDeviceToHost, h->stream));
+    if (pairs_out) JB_HIP(hipMemcpyAsync(pairs_out, h->wit.pair.get(), sizeof(int) * 2 * N, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     int touching = 0;
     for (size_t i = 0; i < N; i++) { if (!(host[i] > 0.f)) touching++; if (clearance_out) clearance_out[i] = host[i]; }
@@ -1567,8 +1550,8 @@ int jb_get_pair_witness(jb_handle* h, uint32_t* overlap_passes, float* min_clear
     if (rc) return rc;
     const size_t N = (size_t)h->cfg.n_envs;
     JB_HIP(hipStreamSynchronize(h->stream));
-    if (overlap_passes) JB_HIP(hipMemcpy(overlap_passes, h->d_wit_count, sizeof(unsigned) * N, hipMemcpyDeviceToHost));
-    if (min_clearance) JB_HIP(hipMemcpy(min_clearance, h->d_wit_min, sizeof(float) * N, hipMemcpyDeviceToHost));
+    if (overlap_passes) JB_HIP(hipMemcpy(overlap_passes, h->wit.count.get(), sizeof(unsigned) * N, hipMemcpyDeviceToHost));
+    if (min_clearance) JB_HIP(hipMemcpy(min_clearance, h->wit.min.get(), sizeof(float) * N, hipMemcpyDeviceToHost));
     return JB_OK;
 }
 int jb_set_model_params(jb_handle* h, const double* params, int32_t n_tables) {
@@ -1595,61 +1578,47 @@ int jb_randomise_models(jb_handle* h, const jb_randomise_cfg* cfg, const double*
     if (!h || !cfg) return fail(JB_E_INVALID, "handle/cfg is NULL");
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
-    {   // one model per env runs the PAIR kernel: refuse up front what JB_FLAG_LEAN cannot run (see check_variant)
-        jb_handle probe = *h;
-        probe.ka.per_env_model = 1; probe.ka.pair = (h->cfg.flags & JB_FLAG_NO_PAIR) ? 0 : 1;
-        int rc0 = check_variant(&probe);
-        if (rc0) return rc0;
-    }
+    // one model per env runs the PAIR kernel: refuse up front what JB_FLAG_LEAN cannot run (see check_variant)
+    const int pair = (h->cfg.flags & JB_FLAG_NO_PAIR) ? 0 : 1;
+    { int rc = check_variant(h->ka.lean, pair, 1, h->ka.epw); if (rc) return rc; }
     JB_HIP(hipStreamSynchronize(h->stream));
     if (!h->d_spec) {
-        JB_HIP(hipMalloc(&h->d_spec, sizeof(JbNominalSpec)));
-        JB_HIP(hipMemcpy(h->d_spec, &JB_NOMINAL_SPEC, sizeof(JbNominalSpec), hipMemcpyHostToDevice));
+        Dev<JbNominalSpec> spec;
+        JB_HIP(spec.alloc(1)); JB_HIP(hipMemcpy(spec.get(), &JB_NOMINAL_SPEC, sizeof(JbNominalSpec), hipMemcpyHostToDevice));
+        h->d_spec = std::move(spec);
     }
-    // The tables are generated into a FRESH buffer and swapped into the handle only after the kernel succeeded: a failure on the
-    // way (the 5 KB x N params_out allocation is the likeliest) leaves the handle on the model it had, never on freed or
-    // half-written tables.
-    float* d_tables = nullptr;
-    double *d_off_in = nullptr, *d_par = nullptr, *d_off_out = nullptr; int *d_att = nullptr, *d_status = nullptr;
-    int rc = JB_OK, status = 0;
-    auto cleanup = [&]() { if (d_tables) hipFree(d_tables); if (d_off_in) hipFree(d_off_in); if (d_par) hipFree(d_par); if (d_off_out) hipFree(d_off_out); if (d_att) hipFree(d_att); if (d_status) hipFree(d_status); };
-#define JB_TRY(call) do { hipError_t _e = (call); if (_e != hipSuccess) { cleanup(); return fail(JB_E_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); } } while (0)
-    JB_TRY(hipMalloc(&d_tables, N * LM_TABLE * sizeof(float)));
-    JB_TRY(hipMalloc(&d_status, sizeof(int)));
-    JB_TRY(hipMemset(d_status, 0, sizeof(int)));
-    if (offsets_in) { JB_TRY(hipMalloc(&d_off_in, sizeof(double) * N * AO_COUNT)); JB_TRY(hipMemcpy(d_off_in, offsets_in, sizeof(double) * N * AO_COUNT, hipMemcpyHostToDevice)); }
-    if (params_out) JB_TRY(hipMalloc(&d_par, sizeof(double) * N * JB_NPARAM));
-    if (offsets_out) JB_TRY(hipMalloc(&d_off_out, sizeof(double) * N * AO_COUNT));
-    if (attempts_out) JB_TRY(hipMalloc(&d_att, sizeof(int) * N));
+    // The tables are generated into a FRESH buffer and installed only after the kernel succeeded: a failure on the way (the 5 KB x N
+    // params_out allocation is the likeliest) leaves the handle on the model it had, never on freed or half-written tables.
+    Dev<float> d_tables;
+    Dev<double> d_off_in, d_par, d_off_out;
+    Dev<int> d_att, d_status;
+    JB_HIP(d_tables.alloc(N * LM_TABLE));
+    JB_HIP(d_status.alloc(1));
+    JB_HIP(hipMemset(d_status.get(), 0, sizeof(int)));
+    if (offsets_in) { JB_HIP(d_off_in.alloc(N * AO_COUNT)); JB_HIP(hipMemcpy(d_off_in.get(), offsets_in, sizeof(double) * N * AO_COUNT, hipMemcpyHostToDevice)); }
+    if (params_out) JB_HIP(d_par.alloc(N * JB_NPARAM));
+    if (offsets_out) JB_HIP(d_off_out.alloc(N * AO_COUNT));
+    if (attempts_out) JB_HIP(d_att.alloc(N));
     RndArgs a;
     a.n = (int)N; a.flags = cfg->flags; a.max_attempts = cfg->max_attempts > 0 ? cfg->max_attempts : 64;
     a.seed = cfg->seed; a.env_offset = h->cfg.env_offset;
     for (int i = 0; i < 3; i++) { a.sd.legs[i] = cfg->sd_legs[i]; a.sd.mass_pos[i] = cfg->sd_mass_pos[i]; }
     a.sd.core1_density = cfg->sd_core1_density; a.sd.core2_density = cfg->sd_core2_density; a.sd.global_density = cfg->sd_global_density; a.sd.gear = cfg->sd_gear;
     a.min_mass_clearance = cfg->min_mass_clearance;
-    a.spec = h->d_spec; a.offsets_in = d_off_in; a.tables = d_tables; a.params_out = d_par; a.offsets_out = d_off_out; a.attempts_out = d_att; a.status = d_status;
+    a.spec = h->d_spec.get(); a.offsets_in = d_off_in.get(); a.tables = d_tables.get(); a.params_out = d_par.get(); a.offsets_out = d_off_out.get();
+    a.attempts_out = d_att.get(); a.status = d_status.get();
     hipLaunchKernelGGL(jb_randomise_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, a);
-    JB_TRY(hipGetLastError());
-    JB_TRY(hipStreamSynchronize(h->stream));
-    JB_TRY(hipMemcpy(&status, d_status, sizeof(int), hipMemcpyDeviceToHost));
-    if (status == 0) {
-        if (params_out) JB_TRY(hipMemcpy(params_out, d_par, sizeof(double) * N * JB_NPARAM, hipMemcpyDeviceToHost));
-        if (offsets_out) JB_TRY(hipMemcpy(offsets_out, d_off_out, sizeof(double) * N * AO_COUNT, hipMemcpyDeviceToHost));
-        if (attempts_out) JB_TRY(hipMemcpy(attempts_out, d_att, sizeof(int) * N, hipMemcpyDeviceToHost));
-    }
-#undef JB_TRY
-    if (status != 0) {      // the handle keeps the model it had
-        cleanup();
+    JB_HIP(hipGetLastError());
+    JB_HIP(hipStreamSynchronize(h->stream));
+    int status = 0;
+    JB_HIP(hipMemcpy(&status, d_status.get(), sizeof(int), hipMemcpyDeviceToHost));
+    if (status != 0)      // the handle keeps the model it had
         return fail(JB_E_MODEL, status == -30 ? "randomise: no draw cleared min_mass_clearance within max_attempts for some env" : "randomise: a generated model is not supported by the kernel (code " + std::to_string(status) + ")");
-    }
-    if (h->d_model) hipFree(h->d_model);          // (the stream is idle: synchronised above)
-    h->d_model = d_tables; h->model_tables = N;
-    d_tables = nullptr;
-    cleanup();
-    h->ka.lane_model = h->d_model;
-    h->ka.per_env_model = 1;
-    h->ka.pair = (h->cfg.flags & JB_FLAG_NO_PAIR) ? 0 : 1;
-    return rc;
+    if (params_out) JB_HIP(hipMemcpy(params_out, d_par.get(), sizeof(double) * N * JB_NPARAM, hipMemcpyDeviceToHost));
+    if (offsets_out) JB_HIP(hipMemcpy(offsets_out, d_off_out.get(), sizeof(double) * N * AO_COUNT, hipMemcpyDeviceToHost));
+    if (attempts_out) JB_HIP(hipMemcpy(attempts_out, d_att.get(), sizeof(int) * N, hipMemcpyDeviceToHost));
+    install_model(h, std::move(d_tables), 1, pair);      // (the stream is idle: synchronised above)
+    return JB_OK;
 }
 // host-only helpers (no GPU): the native compiler / validity check on ONE model - what the device kernel runs per env
 int jb_model_compile_host(const double* offsets, int32_t flags, double* params_out) {
@@ -1716,6 +1685,21 @@ int jb_comm_destroy(jb_handle* h) {
     if (h->comm) { JB_ENTER(h); hipDeviceSynchronize(); JB_NCCL(g_rccl.CommDestroy(h->comm)); h->comm = nullptr; h->comm_nmax = 0; }
     return JB_OK;
 }
+// The grouped exchange with rank 0 behind the gathers and the scatter, `count` floats per rank: rank 0 exchanges block r of `all`
+// [n_ranks, count] with rank r, and every rank its own block `mine` with rank 0 - a gather sends `mine` and rank 0 receives into `all`,
+// a scatter the reverse.  A failed Send/Recv must not leave the RCCL group open: the group is closed, then the first error is reported.
+static int rccl_exchange(jb_handle* h, bool gather, const float* all, const float* mine, size_t count, void* stream, int32_t use_stream, const char* what) {
+    hipStream_t st = use_stream ? (hipStream_t)stream : h->stream;
+    JB_NCCL(g_rccl.GroupStart());
+    int err = 0;
+    if (h->comm_rank == 0)
+        for (int r = 0; r < h->comm_ranks && !err; r++)      // (const_cast: the receiving side of a gather)
+            err = gather ? g_rccl.Recv(const_cast<float*>(all) + (size_t)r * count, count, 7 /*ncclFloat*/, r, h->comm, st) : g_rccl.Send(all + (size_t)r * count, count, 7 /*ncclFloat*/, r, h->comm, st);
+    if (!err) err = gather ? g_rccl.Send(mine, count, 7 /*ncclFloat*/, 0, h->comm, st) : g_rccl.Recv(const_cast<float*>(mine), count, 7 /*ncclFloat*/, 0, h->comm, st);
+    const int end = g_rccl.GroupEnd();
+    if (err || end) return fail(JB_E_HIP, std::string(what) + (g_rccl.GetErrorString ? g_rccl.GetErrorString(err ? err : end) : "RCCL error"));
+    return JB_OK;
+}
 // the same exchange for a block of `count` floats per rank (equal on every rank): what a fused K-step rollout returns, [K, N_local, D+2]
 int jb_gather_block_device(jb_handle* h, const float* d_src, float* d_all, int64_t count, void* stream, int32_t use_stream) {
     if (!h || !d_src || count < 1) return fail(JB_E_INVALID, "handle/src is NULL or count < 1");
@@ -1723,15 +1707,7 @@ int jb_gather_block_device(jb_handle* h, const float* d_src, float* d_all, int64
     if (h->comm_rank == 0 && !d_all) return fail(JB_E_INVALID, "rank 0 needs the receive buffer [n_ranks, count]");
     JB_ENTER(h);
     RoctxRange range("jb_gather_block");
-    hipStream_t st = use_stream ? (hipStream_t)stream : h->stream;
-    JB_NCCL(g_rccl.GroupStart());
-    int err = 0;              // a failed Send/Recv must not leave the RCCL group open: close it, then report the first error
-    if (h->comm_rank == 0)
-        for (int r = 0; r < h->comm_ranks && !err; r++) err = g_rccl.Recv(d_all + (size_t)r * (size_t)count, (size_t)count, 7 /*ncclFloat*/, r, h->comm, st);
-    if (!err) err = g_rccl.Send(d_src, (size_t)count, 7 /*ncclFloat*/, 0, h->comm, st);
-    const int end = g_rccl.GroupEnd();
-    if (err || end) return fail(JB_E_HIP, std::string("RCCL block gather: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(err ? err : end) : "RCCL error"));
-    return JB_OK;
+    return rccl_exchange(h, true, d_all, d_src, (size_t)count, stream, use_stream, "RCCL block gather: ");
 }
 int jb_gather_rows_device(jb_handle* h, const float* d_rows, float* d_all, void* stream, int32_t use_stream) {
     if (!h || !d_rows) return fail(JB_E_INVALID, "handle/rows is NULL");
@@ -1739,17 +1715,9 @@ int jb_gather_rows_device(jb_handle* h, const float* d_rows, float* d_all, void*
     if (h->comm_rank == 0 && !d_all) return fail(JB_E_INVALID, "rank 0 needs the receive buffer [n_ranks, N_local, D+2]");
     JB_ENTER(h);
     RoctxRange range("jb_gather_rows");
-    hipStream_t st = use_stream ? (hipStream_t)stream : h->stream;
     // every rank posts blocks of the longest shard (jb_comm_set_shards; without it the shards are equal by contract)
     const size_t count = (size_t)(h->comm_nmax > 0 ? h->comm_nmax : h->cfg.n_envs) * (size_t)(h->D + 2);
-    JB_NCCL(g_rccl.GroupStart());
-    int err = 0;              // a failed Send/Recv must not leave the RCCL group open: close it, then report the first error
-    if (h->comm_rank == 0)
-        for (int r = 0; r < h->comm_ranks && !err; r++) err = g_rccl.Recv(d_all + (size_t)r * count, count, 7 /*ncclFloat*/, r, h->comm, st);
-    if (!err) err = g_rccl.Send(d_rows, count, 7 /*ncclFloat*/, 0, h->comm, st);
-    const int end = g_rccl.GroupEnd();
-    if (err || end) return fail(JB_E_HIP, std::string("RCCL row gather: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(err ? err : end) : "RCCL error"));
-    return JB_OK;
+    return rccl_exchange(h, true, d_all, d_rows, count, stream, use_stream, "RCCL row gather: ");
 }
 int jb_scatter_actions_device(jb_handle* h, const float* d_all, float* d_local, int64_t count, void* stream, int32_t use_stream) {
     if (!h || !d_local || count < 1) return fail(JB_E_INVALID, "handle/local is NULL or count < 1");
@@ -1759,15 +1727,7 @@ int jb_scatter_actions_device(jb_handle* h, const float* d_all, float* d_local, 
         return fail(JB_E_INVALID, "jb_scatter_actions_device: count must be the longest shard's envs (" + std::to_string(h->comm_nmax > 0 ? h->comm_nmax : h->cfg.n_envs) + "), the same on every rank");
     JB_ENTER(h);
     RoctxRange range("jb_scatter_actions");
-    hipStream_t st = use_stream ? (hipStream_t)stream : h->stream;
-    JB_NCCL(g_rccl.GroupStart());
-    int err = 0;              // (as in the gathers: the group is closed before an error is reported)
-    if (h->comm_rank == 0)
-        for (int r = 0; r < h->comm_ranks && !err; r++) err = g_rccl.Send(d_all + (size_t)r * (size_t)count, (size_t)count, 7 /*ncclFloat*/, r, h->comm, st);
-    if (!err) err = g_rccl.Recv(d_local, (size_t)count, 7 /*ncclFloat*/, 0, h->comm, st);
-    const int end = g_rccl.GroupEnd();
-    if (err || end) return fail(JB_E_HIP, std::string("RCCL action scatter: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(err ? err : end) : "RCCL error"));
-    return JB_OK;
+    return rccl_exchange(h, false, d_all, d_local, (size_t)count, stream, use_stream, "RCCL action scatter: ");
 }
 
 }  // extern "C"

@@ -382,6 +382,63 @@ extern "C" void jbh_device_guard_probe(int cur, int target, int fail_set, int ea
     out[2] = StubDeviceApi::cur; out[3] = StubDeviceApi::n_set;
 }
 
+// ---- jb_owned.hpp against a stub allocator whose k-th allocation fails (the library instantiates it with hipMalloc / hipFree & co.)
+#include <set>
+#include "../jitterbug_amd/csrc/jb_owned.hpp"
+namespace {
+struct StubAllocApi {
+    static int n_alloc, fail_at, n_free, bad_free;
+    static std::set<void*> live;
+    static char arena[64];
+    template <typename T> static int alloc(T** p, size_t) {
+        if (++n_alloc == fail_at) return 2;                  // (the runtime's "out of memory")
+        *p = reinterpret_cast<T*>(arena + n_alloc % 64);      // a distinct fake address per live allocation
+        live.insert(*p);
+        return 0;
+    }
+    template <typename T> static void free(T* p) { n_free++; if (!live.erase(p)) bad_free++; }
+};
+int StubAllocApi::n_alloc = 0, StubAllocApi::fail_at = 0, StubAllocApi::n_free = 0, StubAllocApi::bad_free = 0;
+std::set<void*> StubAllocApi::live;
+char StubAllocApi::arena[64];
+struct StubGroup { jb::Owned<float*, StubAllocApi> a, b; jb::Owned<int*, StubAllocApi> c; };
+// what jb_api.hip does for a lazily created group: allocate into a local group, move it into the target only when all went well
+int fill_group(StubGroup& target) {
+    if (target.a) return 0;
+    StubGroup g;
+    if (int rc = g.a.alloc(4)) return rc;
+    if (int rc = g.b.alloc(8)) return rc;
+    if (int rc = g.c.alloc(2)) return rc;
+    target = std::move(g);
+    return 0;
+}
+bool group_empty(const StubGroup& g) { return !g.a && !g.b && !g.c && !g.a.size() && !g.b.size() && !g.c.size(); }
+}
+// The k-th allocation (1..3) of a group fails, then the group is built again with nothing failing, rebuilt over a full target, and
+// destroyed.  out = [rc of the failed attempt, target empty after it, live allocations after it, rc of the retry, target filled,
+// live after it, live after the rebuild, live after destruction, allocations, frees, frees of an address not live]
+extern "C" void jbh_owned_group_probe(int k, int* out) {
+    StubAllocApi::n_alloc = StubAllocApi::n_free = StubAllocApi::bad_free = 0;
+    StubAllocApi::live.clear();
+    {
+        StubGroup target;
+        StubAllocApi::fail_at = k;
+        out[0] = fill_group(target);
+        out[1] = group_empty(target);
+        out[2] = (int)StubAllocApi::live.size();
+        StubAllocApi::fail_at = 0;
+        out[3] = fill_group(target);
+        out[4] = target.a.size() == 4 && target.b.size() == 8 && target.c.size() == 2 && target.a.get() != target.b.get();
+        out[5] = (int)StubAllocApi::live.size();
+        StubGroup fresh;
+        fresh.a = std::move(target.a);       // the old buffers go through moves...
+        target = std::move(fresh);           // ...and a move assignment over a filled target frees what it held
+        out[6] = (int)StubAllocApi::live.size();
+    }
+    out[7] = (int)StubAllocApi::live.size();
+    out[8] = StubAllocApi::n_alloc; out[9] = StubAllocApi::n_free; out[10] = StubAllocApi::bad_free;
+}
+
 // ---- the pair narrow phase of jb_sim.hpp (mass ellipsoid against the upper cylinder of `leg`) on a posed model, fp64 or fp32, for the
 // comparison with the oracle's pair_geometric: inputs are the two geoms in WORLD coordinates, out = [dist, n(3), pos(3)]
 extern "C" void jbh_pair_narrow(const double* ce, const double* Re, const double* sz, const double* cc, const double* ua, double rad, double half, int use_float, double* out) {

@@ -110,6 +110,24 @@ def test_entry_points_hand_the_callers_device_back():
     assert "DeviceGuard<HipDeviceApi>" in src and "JB_HIP(hipSetDevice" not in src      # no entry point switches without the guard
 
 
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_lazy_group_is_all_or_nothing_and_frees_once(k):
+    """a lazily created group of the handle (async staging, witness, ...) is allocated into local owners and moved into
+    the handle only when every allocation succeeded.  The owner (csrc/jb_owned.hpp) is run here against a stub whose k-th allocation fails."""
+    import ctypes as C
+    import tests.build_harness as bh
+    lib = C.CDLL(bh.build())
+    out = (C.c_int * 11)()
+    lib.jbh_owned_group_probe(k, out)
+    rc_fail, empty, live_fail, rc_ok, filled, live_ok, live_rebuilt, live_end, n_alloc, n_free, bad_free = list(out)
+    assert rc_fail != 0 and empty == 1 and live_fail == 0        # the failed group left its target empty and freed what it had taken
+    assert rc_ok == 0 and filled == 1 and live_ok == 3            # a later attempt fills the target
+    assert live_rebuilt == 1 and live_end == 0                    # a move assignment frees what the target held; destruction frees the rest
+    assert n_alloc == k + 3 and n_free == n_alloc - 1 and bad_free == 0      # every successful allocation freed exactly once, moves included
+    src = open(bh.os.path.join(bh.HERE, "..", "jitterbug_amd", "csrc", "jb_api.hip")).read()
+    assert all(src.count(f) == 1 for f in ("hipFree(", "hipHostFree(", "hipEventDestroy("))      # only in the owner's HIP instantiation
+
+
 def test_build_is_keyed_on_the_source_hash_not_on_file_times(tmp_path):
     """the library carries the sha256 of the sources it was built from; needs_build() compares that with the sources
     as they are (a comment edited in a copy of csrc/ makes it true, restoring the text makes it false again - whatever the mtimes), and
