@@ -2484,7 +2484,11 @@ JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                     MK warm_ok = mand(near_pair, gt(sc.ld(sc.pd + 11), V(0.5)));
                     if (any_lane(warm_ok)) {
                         const MK conv = pair_narrow_warm<V>(pe, Re, ldc3(m, LM_PE_S), uc, ua, ldc(m, LM_UC_R), uh, wt, wlam, pdist, pn, ppos);
-                        warm_ok = mand(warm_ok, conv);
+                        // ... and only where the overlap is shallower than the leg's radius.  Deeper (the leg's axis inside the mass) the cold
+                        // scheme's fixed counts do NOT reach the root, and what they do reach is the contact's definition (jb_oracle.c
+                        // pair_geometric): Newton from the previous substep converges to the root itself, another contact - off by up to
+                        // 4.5e-2 in an observation entry, in fp64 as in fp32.  Such a lane takes the cold scheme.
+                        warm_ok = mand(mand(warm_ok, conv), mnot(lt(pdist, -ldc(m, LM_UC_R))));
                     }
 #if !defined(__HIPCC__)
                     if (sc.grp == 0) g_pair_narrow_stats[any_lane(mand(near_pair, mnot(warm_ok))) ? 1 : 0]++;

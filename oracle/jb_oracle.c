@@ -82,8 +82,17 @@ typedef struct {
     double margin_min;   /* smallest |distance| of any contact CANDIDATE point (touching or not) seen by collide(): how close the
                             step came to a contact switching on or off exactly at a substep boundary.  Contact activation is the
                             one discontinuity of the model (dist < 0, MuJoCo margin 0): a step whose margin_min is below the
-                            position error of an fp32 run can legitimately differ from it by one substep's contact impulse. */
+                            position error of an fp32 run can legitimately differ from it by one substep's contact impulse.
+                            (Forced to 0 by a DEEP pair overlap, see `deep`: two unrelated conditions in one number, kept for its callers.) */
+    double switch_min;   /* the same minimum WITHOUT the forced zeros: the distance from a contact switch alone */
+    double switch_src[3];/* ... and split by what came close: [0] floor candidates, [1] mass - leg pairs, [2] thread - leg pairs */
+    double narrow_resid; /* largest residual the mass - leg narrow phase's fixed counts left on a LIVE contact (g_pair_resid below) */
+    int deep;            /* 1: in some substep a mass - leg or thread - leg pair overlapped by more than the leg's radius (dist < -r_leg: the
+                            leg's axis inside the mass / the thread).  Not a discontinuity: the contact is simulated and compared like any other. */
 } jbo_stats;
+
+/* what collide() reports about the conditioning of one substep (folded into jbo_stats by substep()) */
+typedef struct { double margin, sw[3]; int deep; double resid; } Cond;
 
 /* ------------------------------------------------------------------ small math */
 static inline void cross3(double* o, const double* a, const double* b) {
@@ -543,6 +552,10 @@ static double pair_eval(PairEval* w, double t, int iters) {
     for (int i = 0; i < 3; i++) w->g[i] = w->x[i] / (w->s2[i] + w->lam);
     return dot3(w->g, w->ul) / sqrt(dot3(w->g, w->g));
 }
+/* how far the fixed counts of the last pair_geometric() on this thread stayed from the root they iterate towards: |f(t)| = |u . n| at the
+ * returned axis point (0 where the point is pinned at an end of the segment) and |N^2(lam) - 1| of the multiplier.  Round-off on shallow
+ * contacts; where it is not, the returned contact is what the counts reach, not the root - and depends on every rounding on the way. */
+static _Thread_local double g_pair_resid;
 static int pair_geometric(const CGeom* e, const CGeom* c, double* dist, double* n, double* pos) {
     PairEval w;
     double d[3], ax[3] = {c->R[2], c->R[5], c->R[8]};
@@ -580,7 +593,13 @@ static int pair_geometric(const CGeom* e, const CGeom* c, double* dist, double* 
         fc = pair_eval(&w, tc, 4);
     }
     tc = at_a ? a0 : (at_b ? fmax(b0, a0) : tc);
-    (void)pair_eval(&w, tc, 5);
+    double ff = pair_eval(&w, tc, 5);
+    {
+        double N2 = 0;
+        for (int i = 0; i < 3; i++) { double ia = 1.0 / (w.s2[i] + w.lam); N2 += w.s2[i] * w.x[i] * w.x[i] * ia * ia; }
+        int pinned = at_a || at_b || (tc <= lo_t && ff >= 0) || (tc >= hi_t && ff <= 0);
+        g_pair_resid = fmax(pinned ? 0.0 : fabs(ff), fabs(N2 - 1.0));
+    }
     double gg = dot3(w.g, w.g), gl = sqrt(gg), nl[3], pl[3];
     *dist = w.lam * gl - rad;
     for (int i = 0; i < 3; i++) { nl[i] = w.g[i] / gl; pl[i] = w.x[i] - 0.5 * w.lam * w.g[i] - 0.5 * rad * nl[i]; }
@@ -687,10 +706,11 @@ static int add_contact(Contact* c, int n, double dist, const double* pos, int bo
     c[n].body2 = -1; c[n].n[0] = 0; c[n].n[1] = 0; c[n].n[2] = 1; c[n].wslot = (geom * 4 + slot) * 4;
     return n + 1;
 }
-#define MARGIN(d) do { double _a = fabs(d); if (_a < *margin) *margin = _a; } while (0)
-static int collide(const double* P, const Kin* k, int feet_only, int pair_contacts, Contact* con, int* overflow, double* margin) {
+#define MARGIN(d) do { double _a = fabs(d); if (_a < cond->margin) cond->margin = _a; if (_a < cond->sw[src]) cond->sw[src] = _a; } while (0)
+#define DEEP() do { cond->margin = 0.0; cond->deep = 1; } while (0)
+static int collide(const double* P, const Kin* k, int feet_only, int pair_contacts, Contact* con, int* overflow, Cond* cond) {
     static const double nz[3] = {0, 0, 1};
-    int n = 0;
+    int n = 0, src = 0;
     for (int g = 0; g < JB_NGEOM; g++) {
         const double* G = P + JB_P_GEOM + g * JB_GEOM_STRIDE;
         int type = (int)G[JB_G_TYPE], b = (int)G[JB_G_BODY];
@@ -777,6 +797,7 @@ static int collide(const double* P, const Kin* k, int feet_only, int pair_contac
          * tight one of this oracle's own (the two AXES within r_thread + r_leg + 0.2 mm of each other - the HIP kernel's broad phase makes the same
          * test) that only spares the narrow phase where the answer is "apart". */
         CGeom th, c;
+        src = 2;
         cgeom_world(P, k, 20, &th);
         for (int l = 0; l < JB_NLEG; l++) {
             int g = 4 + 4 * l;
@@ -788,7 +809,7 @@ static int collide(const double* P, const Kin* k, int feet_only, int pair_contac
             double dist, dir[3], pos[3];
             pair_thread_geometric(&th, &c, JB_THREAD_BISECT, &dist, dir, pos);
             MARGIN(dist);
-            if (dist < -c.sz[0]) MARGIN(0.0);          /* the leg's AXIS inside the thread: counted as ill-conditioned for the fp32 comparison, like the pair below */
+            if (dist < -c.sz[0]) DEEP();               /* the leg's AXIS inside the thread: margin_min forced to 0 and the deep flag set, like the pair below */
             if (dist < 0) {
                 if (n < MAXCON) {
                     con[n].dist = dist; memcpy(con[n].pos, pos, 24); memcpy(con[n].n, dir, 24);
@@ -806,6 +827,7 @@ static int collide(const double* P, const Kin* k, int feet_only, int pair_contac
          * the mass to the leg; bounding spheres first (mj_collideGeoms), then - where MuJoCo runs mjc_Convex = MPR - the geometric
          * contact MPR's output scatters around (pair_geometric above). */
         CGeom e, c;
+        src = 1;
         cgeom_world(P, k, 21, &e);
         for (int l = 0; l < JB_NLEG; l++) {
             int g = 4 + 4 * l;
@@ -826,11 +848,13 @@ static int collide(const double* P, const Kin* k, int feet_only, int pair_contac
             }
             double dist, dir[3], pos[3];
             pair_geometric(&e, &c, &dist, dir, pos);
+            if (dist < 0 && g_pair_resid > cond->resid) cond->resid = g_pair_resid;
             MARGIN(dist);
             /* An overlap deeper than the cylinder radius puts the leg's AXIS inside the mass: the nearest-surface point of an interior point
              * of this flat ellipsoid (3 mm half thickness) is ill-conditioned towards its mid-plane, and no robot could be built that
-             * way - such env-steps count as ill-conditioned for the fp32 comparison (the contact itself is simulated all the same). */
-            if (dist < -c.sz[0]) MARGIN(0.0);
+             * way - margin_min is forced to 0 for such env-steps (the contact itself is simulated all the same); the deep flag reports the
+             * condition on its own, and switch_min stays what it is, so that a comparison can hold this class to a bound of its own. */
+            if (dist < -c.sz[0]) DEEP();
             if (dist < 0) {
                 if (n < MAXCON) {
                     con[n].dist = dist; memcpy(con[n].pos, pos, 24); memcpy(con[n].n, dir, 24);
@@ -902,9 +926,17 @@ static void substep(const double* P, double* qpos, double* qvel, double ctrl, co
     memset(qfc, 0, sizeof qfc);
     Contact con[MAXCON];
     int ncon = 0, overflow = 0;
-    double margin = INFINITY;
-    if (o->contacts) ncon = collide(P, &k, o->feet_only, o->pair_contacts, con, &overflow, &margin);
-    if (st && margin < st->margin_min) st->margin_min = margin;
+    Cond cond = {INFINITY, {INFINITY, INFINITY, INFINITY}, 0, 0.0};
+    if (o->contacts) ncon = collide(P, &k, o->feet_only, o->pair_contacts, con, &overflow, &cond);
+    if (st) {
+        if (cond.margin < st->margin_min) st->margin_min = cond.margin;
+        for (int i = 0; i < 3; i++) {
+            if (cond.sw[i] < st->switch_src[i]) st->switch_src[i] = cond.sw[i];
+            if (cond.sw[i] < st->switch_min) st->switch_min = cond.sw[i];
+        }
+        st->deep |= cond.deep;
+        if (cond.resid > st->narrow_resid) st->narrow_resid = cond.resid;
+    }
     if (dbg) { dbg->ncon = ncon; dbg->nrow = 0; memcpy(dbg->M, M, sizeof M); memcpy(dbg->bias, bias, sizeof bias); memcpy(dbg->tau, tau, sizeof tau); }
 
     if (ncon > 0 || dbg) {
@@ -1397,6 +1429,7 @@ typedef struct {
     double *qpos, *qvel, *target, *warm;
     int *step_count; uint32_t* episode;
     double* margin;      /* [n]: jbo_stats.margin_min of each env's last control step */
+    double* cond;        /* [n, 5]: switch_min, switch_src[3], deep (0 / 1) of each env's last control step */
     jbo_stats stats;
 } jbo_env;
 
@@ -1411,14 +1444,14 @@ jbo_env* jbo_env_create(int n, int task, int random_pose, int nsub, int step_lim
     e->P = malloc(sizeof(double) * np); memcpy(e->P, P, sizeof(double) * np);
     e->qpos = calloc((size_t)n * NQ, sizeof(double)); e->qvel = calloc((size_t)n * NV, sizeof(double));
     e->target = calloc((size_t)n * 3, sizeof(double)); e->warm = calloc((size_t)n * WARM_SIZE, sizeof(double));
-    e->step_count = calloc(n, sizeof(int)); e->episode = calloc(n, sizeof(uint32_t)); e->margin = calloc(n, sizeof(double));
+    e->step_count = calloc(n, sizeof(int)); e->episode = calloc(n, sizeof(uint32_t)); e->margin = calloc(n, sizeof(double)); e->cond = calloc((size_t)n * 6, sizeof(double));
     /* like jb_create: a created env is already in a valid state (reset #0); the first explicit reset is #1 */
     for (int i = 0; i < n; i++) { jbo_reset(envP(e, i), e->task, e->random_pose, e->seed, e->env_offset + (uint64_t)i, 0, e->qpos + (size_t)i * NQ, e->qvel + (size_t)i * NV, e->target + (size_t)i * 3); e->episode[i] = 1; }
     return e;
 }
 void jbo_env_destroy(jbo_env* e) {
     if (!e) return;
-    free(e->P); free(e->qpos); free(e->qvel); free(e->target); free(e->warm); free(e->step_count); free(e->episode); free(e->margin); free(e);
+    free(e->P); free(e->qpos); free(e->qvel); free(e->target); free(e->warm); free(e->step_count); free(e->episode); free(e->margin); free(e->cond); free(e);
 }
 static void env_reset_one(jbo_env* e, int i) {
     jbo_reset(envP(e, i), e->task, e->random_pose, e->seed, e->env_offset + (uint64_t)i, e->episode[i],
@@ -1452,9 +1485,10 @@ void jbo_env_step(jbo_env* e, const double* action, double* obs, double* reward,
 #endif
         for (int i = 0; i < e->n; i++) {
             double* qp = e->qpos + (size_t)i * NQ; double* qv = e->qvel + (size_t)i * NV; double* tg = e->target + (size_t)i * 3;
-            st.margin_min = INFINITY;
+            st.margin_min = st.switch_min = st.switch_src[0] = st.switch_src[1] = st.switch_src[2] = INFINITY; st.deep = 0; st.narrow_resid = 0;
             jbo_step_physics(envP(e, i), qp, qv, action[i], e->nsub, &e->opts, e->warm + (size_t)i * WARM_SIZE, &st);
             e->margin[i] = st.margin_min;
+            { double* c = e->cond + (size_t)i * 6; c[0] = st.switch_min; c[1] = st.switch_src[0]; c[2] = st.switch_src[1]; c[3] = st.switch_src[2]; c[4] = st.deep; c[5] = st.narrow_resid; }
             e->step_count[i]++;
             if (reward) reward[i] = jbo_reward(envP(e, i), e->task, qp, qv, tg);
             int d = e->step_count[i] >= e->step_limit;
@@ -1492,6 +1526,9 @@ void jbo_env_get_counters(const jbo_env* e, int* step_count, uint32_t* episode) 
 }
 void jbo_env_stats(const jbo_env* e, jbo_stats* out) { *out = e->stats; }
 void jbo_env_get_margin(const jbo_env* e, double* out) { memcpy(out, e->margin, sizeof(double) * e->n); }
+/* out [n, 6]: switch margin, its floor / mass-pair / thread-pair parts, deep flag, narrow-phase residual - of each env's last control step */
+void jbo_env_get_conditioning(const jbo_env* e, double* out) { memcpy(out, e->cond, sizeof(double) * 6 * e->n); }
+int jbo_stats_size(void) { return (int)sizeof(jbo_stats); }
 int jbo_max_threads(void) {
 #ifdef _OPENMP
     return omp_get_max_threads();

@@ -53,7 +53,8 @@ class Opts(C.Structure):
 
 class Stats(C.Structure):
     _fields_ = [("ncon_last", C.c_int), ("ncon_max", C.c_int), ("sweeps_total", C.c_int), ("sweeps_max", C.c_int),
-                ("nsolve", C.c_int), ("overflow", C.c_int), ("resid_max", C.c_double), ("margin_min", C.c_double)]
+                ("nsolve", C.c_int), ("overflow", C.c_int), ("resid_max", C.c_double), ("margin_min", C.c_double),
+                ("switch_min", C.c_double), ("switch_src", C.c_double * 3), ("narrow_resid", C.c_double), ("deep", C.c_int)]
 
 
 class Debug(C.Structure):
@@ -99,6 +100,8 @@ def lib():
         L.jbo_env_get_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.jbo_env_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.jbo_env_get_margin.argtypes = [C.c_void_p, _dp]
+        L.jbo_env_get_conditioning.argtypes = [C.c_void_p, _dp]
+        assert L.jbo_stats_size() == C.sizeof(Stats), (L.jbo_stats_size(), C.sizeof(Stats))
         L.jbo_pair_clearance.argtypes = [_dp, _dp, C.c_void_p]
         L.jbo_pair_clearance.restype = C.c_double
         L.jbo_geom_distance.argtypes = [_dp, _dp, C.c_int, C.c_int]
@@ -327,6 +330,15 @@ class OracleEnv:
         m = np.zeros(self.n)
         lib().jbo_env_get_margin(self._h, _p(m))
         return m
+
+    def conditioning(self):
+        """Per env, of the last control step: `switch` - margins() without the zeros a deep pair overlap forces (the distance from a contact
+        switching on or off at a substep boundary, alone) -, its parts `floor` / `mass` / `thread` by what came close (inf: nothing of that
+        kind was a candidate), and `deep` - some substep had a mass - leg or thread - leg pair overlapping by more than the leg's radius.
+        margins() == where(deep, 0, switch)."""
+        c = np.zeros((self.n, 6))
+        lib().jbo_env_get_conditioning(self._h, _p(c))
+        return dict(switch=c[:, 0].copy(), floor=c[:, 1].copy(), mass=c[:, 2].copy(), thread=c[:, 3].copy(), deep=c[:, 4] != 0, narrow_resid=c[:, 5].copy())
 
     def stats(self):
         s = Stats()

@@ -110,18 +110,35 @@ def test_device_compiler_matches_python_on_given_offsets_and_steps_like_the_orac
     np.testing.assert_allclose(out["params"], ref, rtol=1e-8, atol=1e-30)
     o = O.OracleEnv(n, "move_to_pose", ref, seed=6, per_env_model=True)
     np.testing.assert_allclose(env.reset(), o.reset(), rtol=2e-6, atol=2e-6)
-    rs = np.random.default_rng(0)
-    bad = tot = 0
+    from tests.test_gpu_parity import ParityTally, assert_protocol, protocol_message
+    rs, rs2 = np.random.default_rng(0), np.random.default_rng(1000)
+    tally = ParityTally(n)
+    env2 = o2 = None
     for t in range(30):
         a = rs.uniform(-1, 1, size=n)
         env.set_state(*o.get_state())
-        og, _, _, _ = env.step(a)
-        oo, _, _ = o.step(a, auto_reset=False)
-        well = o.margins() >= 3e-8
-        w = np.abs(og - oo) <= 1e-4 * np.abs(oo) + 1e-6
-        bad += (~w[well]).sum(); tot += w[well].size
-    assert bad == 0 and tot > 0.97 * 30 * n * 19
+        og, rg, _, _ = env.step(a)
+        oo, ro, _ = o.step(a, auto_reset=False)
+        ill_bad = tally.add(o, og, oo, rg, ro)
+        if ill_bad.any():
+            # the cascade check, on a second pair of envs with the same device-compiled models: the GPU's next step from its own state
+            if env2 is None:
+                env2 = JitterbugVecEnv(n, "move_to_pose", seed=6, auto_reset=False, time_limit=float("inf"))
+                env2.randomise_models(offsets=offs, **flags)
+                o2 = O.OracleEnv(n, "move_to_pose", ref, seed=6, per_env_model=True)
+                env2.reset(); o2.reset()
+            q2, v2, t2 = env.get_state()
+            env2.set_state(q2, v2, t2); o2.set_state(q2, v2, t2)
+            a2 = rs2.uniform(-1, 1, size=n)
+            tally.cascade(ill_bad, o2, env2.step(a2)[0], o2.step(a2, auto_reset=False)[0])
+    r = tally.result(env.counters()[2].sum())
+    print("device-compiled models, 96 envs x 30 steps:", r)
+    # the whole protocol.  2880 env-steps: the near-switch cap is 0.3 % plus three binomial spreads of a run this size (3 x 0.07 %) - this
+    # test allowed 3 % of the env-steps outside its own 30 nm before
+    assert_protocol(r, well_bad=0)
     env.close()
+    if env2 is not None:
+        env2.close()
 
 
 @pytest.mark.gpu
@@ -193,13 +210,17 @@ def test_config5_shard_8192_device_models_against_the_oracle(variant):
     rng = np.random.default_rng(12)
     # Three classes of robots in the subset, by how deep the mass ever gets into a leg during THIS rollout (the oracle's own narrow phase
     # on the pre-step states): 0 never touches; 1 touches by less than the leg's radius (a contact MuJoCo's MPR and the geometric
-    # narrow phase agree on); 2 deeper (the leg's axis inside the mass: a robot that could not be built; the fixed-count narrow phase
-    # is only first-order there).  The north-star tolerance is asserted on classes 0 and 1; the loose bound is for class 2 alone.
+    # narrow phase agree on); 2 deeper (the leg's axis inside the mass: a robot that could not be built).  The north-star tolerance is asserted
+    # on all three; the env-steps of class-2 robots in which the overlap IS that deep are the protocol's deep class (the oracle's own flag,
+    # OracleEnv.conditioning()), held to the strict line by the tally below, not merely counted.
     LEG_RADIUS = 0.00061          # reference jitterbug.xml:58-100: every leg cylinder has size 0.00061
     depth = np.zeros(64)
     bad = np.zeros((3,), dtype=np.int64); tot_c = np.zeros((3,), dtype=np.int64); ill_c = np.zeros((3,), dtype=np.int64)
     rew_err = np.zeros(3); worst_c = np.zeros(3)
     per_step = []
+    from tests.test_gpu_parity import MARGIN_TOL, NARROW_RESID_TOL, ParityTally, assert_protocol, protocol_message
+    tally = ParityTally(64)
+    followed = np.zeros(64, bool)
     for t in range(steps):
         a = rng.uniform(-1, 1, size=n)
         q, v, tg = env.get_state()
@@ -212,22 +233,38 @@ def test_config5_shard_8192_device_models_against_the_oracle(variant):
         og, rg, dg, _ = env.step(a)
         o.set_state(q[idx], v[idx], tg[idx])
         oo, ro, do = o.step(a[idx], auto_reset=False)
-        well = o.margins() >= 3e-8
+        # the GPU runs free, so the cascade check needs no second env: the near-switch env-steps that left the tolerance at step t are followed
+        # into step t + 1, which IS the GPU's next step from its own state
+        tally.cascade(followed, o, og[idx], oo)
+        followed = tally.add(o, og[idx], oo, rg[idx], ro)
+        cond = o.conditioning()
+        # well and deep classes alike - but for the deep env-steps whose narrow phase stops short of its root, which the tally bounds (DEEP_ERROR_CAP)
+        held = (cond["switch"] >= MARGIN_TOL) & ~(cond["deep"] & (cond["narrow_resid"] >= NARROW_RESID_TOL))
         err = np.abs(og[idx].astype(np.float64) - oo)
         w = err <= 1e-4 * np.abs(oo) + 1e-6
-        per_step.append((well.copy(), (~w).sum(1), err.max(1), np.abs(rg[idx] - ro)))
+        per_step.append((held.copy(), (~w).sum(1), err.max(1), np.abs(rg[idx] - ro), cond["deep"].copy(), cond["switch"] < MARGIN_TOL))
     cls = np.where(depth <= 0, 0, np.where(depth < LEG_RADIUS, 1, 2))
-    for well, nbad, emax, rerr in per_step:
+    deep_of_class = np.zeros(3, dtype=np.int64)
+    for well, nbad, emax, rerr, deep, near in per_step:
         for c in range(3):
+            deep_of_class[c] += (deep & (cls == c)).sum()
             m = (cls == c) & well
-            bad[c] += nbad[m].sum(); tot_c[c] += m.sum() * oo.shape[1]; ill_c[c] += ((cls == c) & ~well).sum()
+            bad[c] += nbad[m].sum(); tot_c[c] += m.sum() * oo.shape[1]; ill_c[c] += ((cls == c) & near).sum()
             if m.any():
                 worst_c[c] = max(worst_c[c], emax[m].max()); rew_err[c] = max(rew_err[c], rerr[m].max())
     sizes = [int((cls == c).sum()) for c in range(3)]
     print("config-5 shard [%s]: robots never touching / touching < leg radius (%.2f mm) / deeper: %s; entries of well-conditioned env-steps outside the tolerance %s of %s; "
           "worst error %s; worst reward error %s; ill-conditioned env-steps %s of %d"
           % (variant, 1e3 * LEG_RADIUS, sizes, bad.tolist(), tot_c.tolist(), ["%.1e" % x for x in worst_c], ["%.1e" % x for x in rew_err], ill_c.tolist(), 64 * steps))
+    r = tally.result(env.counters()[2].sum())
+    print("config-5 shard [%s], the protocol over the 64 compared envs:" % variant, r, "deep env-steps per robot class", deep_of_class.tolist())
     assert sizes[0] >= 30 and sizes[1] + sizes[2] >= 10, sizes
+    # the whole protocol over the subset (12 800 env-steps): well and deep classes on the strict line, near-switch env-steps capped at 0.3 %,
+    # bounded and followed into the GPU's next step; `well_bad` as the per-class count below allows (1 + 2)
+    assert_protocol(r, well_bad=3)
+    # (the robot classes come from the pre-step states of every fourth control step, the deep flag from every substep: nearly all deep env-steps
+    #  belong to class-2 robots - measured 818 of 838 -, and those robots have some)
+    assert sizes[2] == 0 or deep_of_class[2] > 0, (deep_of_class, sizes)
     # classes 0 and 1: the north-star tolerance on every entry of every well-conditioned env-step (measured: ONE of 196 574 entries outside
     # it, a near-zero entry off by 3.8e-6 absolute - fp32 rounding, no contact switch involved; the largest ABSOLUTE error of any entry,
     # inside the tolerance or not, 4.7e-6 / 1.0e-5 in the two classes), rewards to 1e-5 (measured 6e-7)
@@ -235,11 +272,13 @@ def test_config5_shard_8192_device_models_against_the_oracle(variant):
     #  magnitude 0.1-0.8 carries 1e-4 relative = 1e-5 ... 8e-5 legitimately; the tolerance itself is what `bad` counts)
     assert bad[0] + bad[1] <= 1 and max(worst_c[0], worst_c[1]) < 3e-5, (bad, worst_c, sizes)
     assert rew_err[0] < 1e-5 and rew_err[1] < 1e-5, rew_err
-    assert ill_c[0] + ill_c[1] < 0.02 * (sizes[0] + sizes[1]) * steps, ill_c          # measured 0.5 %
-    # class 2 (deeper than the leg's radius): a third of its env-steps are ill-conditioned by the oracle's own margin; the well-conditioned
-    # ones hold the tolerance too (measured 0 of 31 540 outside), the others are only bounded in number
+    # class 2 (deeper than the leg's radius): its env-steps, the deep ones included (a third of them), hold the tolerance too
     assert bad[2] <= 2 and worst_c[2] < 1e-4 and rew_err[2] < 1e-4, (bad, worst_c, rew_err)
-    assert ill_c[2] < 0.5 * max(sizes[2], 1) * steps, ill_c
+    # env-steps within MARGIN_TOL of a contact switch: capped over the subset by the protocol above (0.3 %); per robot class, three binomial
+    # spreads of the class's own number of env-steps on top (the nominal share is 0.15 %)
+    for c in range(3):
+        m = sizes[c] * steps
+        assert m == 0 or ill_c[c] <= 0.003 * m + 3 * np.sqrt(0.0015 * m), (c, ill_c, sizes)
     q, v, _ = env.get_state()
     sc, ep, cap = env.counters()
     assert np.isfinite(og).all() and np.isfinite(q).all() and np.isfinite(v).all()

@@ -1,8 +1,18 @@
 """CPU study of the teacher-forced parity outliers (no GPU): the kernel's simulator source compiled for the host in fp32
-(tests/host_harness.cpp) against the fp64 oracle, env-step by env-step, together with the oracle's contact-switch margin
-(jbo_stats.margin_min: the smallest |distance| of any contact candidate at a substep boundary).
-    python tools/flip_study.py [n_envs] [steps] [task]
-Prints the fraction of observation entries inside the north-star tolerance, overall and as a function of the margin."""
+(tests/host_harness.cpp) against the fp64 oracle, env-step by env-step, together with the oracle's conditioning of the step
+(OracleEnv.conditioning(): the contact-switch margin - the smallest |distance| of any contact candidate at a substep boundary - and the
+deep flag of the geom-geom pairs).
+    python tools/flip_study.py [n_envs] [steps] [task]                                   nominal model, ordinary kernel source
+    python tools/flip_study.py --variant pair|pair_lean --inputs augmented|mass|thread [--envs N] [--steps K] [--seed S] [--task T]
+                               [--flat-out] [--skip N] [--deep-only] [--sensitivity]     one model per env, PAIR / LEAN + PAIR kernel source
+Inputs as the GPU tests build them: augmented = augmented_params(N, seed=5); mass = the mass-touching models of
+tests/test_pair_contact.py tiled to N; thread = the thread-touching models of tests/test_thread_contact.py tiled to N.  --flat-out: motor
+flat out, --skip N: that many lead-in steps on the oracle alone (the robots tip over).  --deep-only: the host build runs the deep env-steps
+only (where they are rare).  --sensitivity: for every env-step of the well / deep classes outside the strict tolerance, the ORACLE's own
+step from the same state rounded to fp32 (what an fp32 simulator is handed, but for the height and the quaternion) against its step from
+the fp64 state - how much of the error is the conditioning of the step itself.
+Prints the three classes of tests/test_gpu_parity.py (well / deep / near-switch), the margin table, a per-env table and the outliers."""
+import argparse
 import ctypes as C
 import os
 import sys
@@ -14,42 +24,132 @@ sys.path.insert(0, ROOT)
 from jitterbug_amd import model  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 import tests.build_harness as bh  # noqa: E402
+from tests.test_gpu_parity import MARGIN_TOL, NARROW_RESID_TOL  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 100
-task = sys.argv[3] if len(sys.argv) > 3 else "move_from_origin"
-lib = C.CDLL(bh.build())
-dp = C.POINTER(C.c_double)
-lib.jbh_step.argtypes = [dp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp]
-P = model.default_params()
+BINS = ((0, 1e-9), (1e-9, 1e-8), (1e-8, 3e-8), (3e-8, 1e-7), (1e-7, 3e-7), (3e-7, 1e-6), (1e-6, 1e-5), (1e-5, 1))
 
 
-def hstep(q, v, u, f32=1):
-    q, v, fail = q.copy(), v.copy(), np.zeros(1)
-    rc = lib.jbh_step(P.ctypes.data_as(dp), q.ctypes.data_as(dp), v.ctypes.data_as(dp), float(u), 50, 1, 20, 1, f32, fail.ctypes.data_as(dp))
-    assert rc == 0
-    qn = q[3:7] / np.linalg.norm(q[3:7]); q[3:7] = qn
-    return q, v
+def nominal(n, steps, task):
+    lib = C.CDLL(bh.build())
+    dp = C.POINTER(C.c_double)
+    lib.jbh_step.argtypes = [dp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+    P = model.default_params()
+
+    def hstep(q, v, u, f32=1):
+        q, v, fail = q.copy(), v.copy(), np.zeros(1)
+        rc = lib.jbh_step(P.ctypes.data_as(dp), q.ctypes.data_as(dp), v.ctypes.data_as(dp), float(u), 50, 1, 20, 1, f32, fail.ctypes.data_as(dp))
+        assert rc == 0
+        qn = q[3:7] / np.linalg.norm(q[3:7]); q[3:7] = qn
+        return q, v
+
+    env = O.OracleEnv(n, task, P, seed=3)
+    env.reset()
+    rng = np.random.default_rng(3)
+    rows = []
+    for t in range(steps):
+        a = rng.uniform(-1, 1, size=n)
+        q0, v0, tg = env.get_state()
+        oo, _, _ = env.step(a, auto_reset=False)
+        mar = env.margins()
+        for i in range(n):
+            qf, vf = hstep(q0[i], v0[i], np.float32(a[i]))          # (the harness splits the fp64 state into hi + lo words like jb_set_state)
+            of = O.observation(P, task, qf, vf, tg[i])
+            err = np.abs(of - oo[i])
+            ok = err <= 1e-4 * np.abs(oo[i]) + 1e-6
+            rows.append((mar[i], ok.mean(), err.max()))
+    rows = np.array(rows)
+    print("env-steps %d; entries within tolerance %.5f; env-steps fully within %.5f; worst %.3g" % (len(rows), rows[:, 1].mean(), (rows[:, 1] == 1).mean(), rows[:, 2].max()))
+    for lo, hi in BINS:
+        m = (rows[:, 0] >= lo) & (rows[:, 0] < hi)
+        if m.any():
+            print("margin [%.0e, %.0e): %6d env-steps (%.2f %%), fully within tolerance %.4f, worst error %.3g" % (lo, hi, m.sum(), 100 * m.mean(), (rows[m, 1] == 1).mean(), rows[m, 2].max()))
 
 
-env = O.OracleEnv(n, task, P, seed=3)
-env.reset()
-rng = np.random.default_rng(3)
-rows = []
-for t in range(steps):
-    a = rng.uniform(-1, 1, size=n)
-    q0, v0, tg = env.get_state()
-    oo, _, _ = env.step(a, auto_reset=False)
-    mar = env.margins()
-    for i in range(n):
-        qf, vf = hstep(q0[i], v0[i], np.float32(a[i]))          # (the harness splits the fp64 state into hi + lo words like jb_set_state)
-        of = O.observation(P, task, qf, vf, tg[i])
-        err = np.abs(of - oo[i])
-        ok = err <= 1e-4 * np.abs(oo[i]) + 1e-6
-        rows.append((mar[i], ok.mean(), err.max()))
-rows = np.array(rows)
-print("env-steps %d; entries within tolerance %.5f; env-steps fully within %.5f; worst %.3g" % (len(rows), rows[:, 1].mean(), (rows[:, 1] == 1).mean(), rows[:, 2].max()))
-for lo, hi in ((0, 1e-9), (1e-9, 1e-8), (1e-8, 3e-8), (3e-8, 1e-7), (1e-7, 3e-7), (3e-7, 1e-6), (1e-6, 1e-5), (1e-5, 1)):
-    m = (rows[:, 0] >= lo) & (rows[:, 0] < hi)
-    if m.any():
-        print("margin [%.0e, %.0e): %6d env-steps (%.2f %%), fully within tolerance %.4f, worst error %.3g" % (lo, hi, m.sum(), 100 * m.mean(), (rows[m, 1] == 1).mean(), rows[m, 2].max()))
+def models(inputs, n):
+    from jitterbug_amd import augmented_jitterbug as aj
+    if inputs == "augmented":
+        return aj.augmented_params(n, seed=5)
+    if inputs == "mass":
+        from tests.test_pair_contact import mass_touching_models
+        ms = mass_touching_models()
+    else:
+        from tests.test_thread_contact import _touching_models
+        ms = _touching_models(16, seed=11)
+    return np.stack([ms[i % len(ms)][0] for i in range(n)])
+
+
+def sensitivity(P, task, seed, steps, flat_out, skip, wanted):
+    """the oracle against itself: its step from the pre-step state rounded to fp32 (height and quaternion kept) vs from the fp64 state"""
+    n = len(P)
+    o = O.OracleEnv(n, task, P, seed=seed, per_env_model=True)
+    o.reset()
+    rng = np.random.default_rng(seed)
+    out = {}
+    for t in range(-skip, steps):
+        a = np.ones(n) if flat_out else rng.uniform(-1, 1, size=n)
+        q0, v0, tg = o.get_state()
+        oo, _, _ = o.step(a, auto_reset=False)
+        for i in [i for (i, tt) in wanted if tt == t]:
+            q = q0[i].copy(); v = v0[i].astype(np.float32).astype(np.float64)
+            q[:2] = q[:2].astype(np.float32); q[7:] = q[7:].astype(np.float32)
+            q1, v1 = O.step_physics(P[i], q, v, float(np.float32(a[i])), 50, O.default_opts())
+            out[(i, t)] = float(np.abs(O.observation(P[i], task, q1, v1, tg[i]) - oo[i]).max())
+    return out
+
+
+def pair(args):
+    from tests.test_pair_contact import host_pair_vs_oracle
+    P = models(args.inputs, args.envs)
+    rows, failed = host_pair_vs_oracle(args.variant, P, args.task, args.seed, args.steps, flat_out=args.flat_out, skip=args.skip, deep_only=args.deep_only)
+    env, step, switch, deep, bad, strict, worst, resid = rows.T
+    deep = deep != 0
+    unconv = resid >= NARROW_RESID_TOL
+    near = switch < MARGIN_TOL
+    print("# %s kernel source, host fp32, 4 lane groups; inputs %s, %d envs x %d steps, task %s, seed %d, %s%s" % (args.variant, args.inputs, args.envs, args.steps, args.task, args.seed,
+          "motor flat out after %d lead-in steps on the oracle" % args.skip if args.flat_out else "uniform actions", "; the deep env-steps only" if args.deep_only else ""))
+    print("env-steps %d; failure flags raised %d; MARGIN_TOL %.1f nm" % (len(rows), failed, MARGIN_TOL * 1e9))
+    for name, m in (("well", ~near & ~deep), ("deep", ~near & deep), (" converged", ~near & deep & ~unconv), (" unconverged", ~near & deep & unconv), ("near-switch", near)):
+        if m.any():
+            print("class %-12s: %6d env-steps (%.2f %%) | entries outside 1e-4 rel + 1e-6 abs %d | strict (1e-5 abs) %d in %d env-steps | worst error %.3g"
+                  % (name, m.sum(), 100 * m.mean(), bad[m].sum(), strict[m].sum(), (strict[m] > 0).sum(), worst[m].max()))
+        else:
+            print("class %-12s: none" % name)
+    print("(deep, converged / unconverged: the residual the oracle's fixed-count narrow phase left on a live mass - leg contact below / not below %.0e; largest on an env-step that is not deep: %.1e)"
+          % (NARROW_RESID_TOL, resid[~deep].max() if (~deep).any() else 0.0))
+    viol = strict > 0
+    print("largest switch margin of an env-step outside the strict tolerance that is not deep (flip_margin_max of the well class's complement): %.2f nm"
+          % (1e9 * switch[viol & ~deep].max() if (viol & ~deep).any() else 0.0))
+    for lo, hi in BINS:
+        m = (switch >= lo) & (switch < hi)
+        if m.any():
+            print("switch margin [%.0e, %.0e): %6d env-steps (%.2f %%), deep %5d, strictly within tolerance %.4f, worst error %.3g" % (lo, hi, m.sum(), 100 * m.mean(), (m & deep).sum(), (strict[m] == 0).mean(), worst[m].max()))
+    print("per env (those with a deep env-step or one outside the strict tolerance): env | env-steps | deep | near-switch | strict violations well / deep / near-switch | worst well / deep")
+    for i in np.unique(env[deep | viol]).astype(int):
+        m = env == i
+        w, d = m & ~near & ~deep, m & ~near & deep
+        print("  env %4d | %4d | %4d | %3d | %d / %d / %d | %.2g / %.2g" % (i, m.sum(), (m & deep).sum(), (m & near).sum(), (viol & w).sum(), (viol & d).sum(), (viol & m & near).sum(),
+              worst[w].max() if w.any() else 0, worst[d].max() if d.any() else 0))
+    held = viol & ~near
+    sens = sensitivity(P, args.task, args.seed, args.steps, args.flat_out, args.skip, {(int(e), int(t)) for e, t in zip(env[held], step[held])}) if args.sensitivity and held.any() else {}
+    print("env-steps of the well / deep classes outside the strict tolerance: %d" % held.sum())
+    for r in rows[held]:
+        k = (int(r[0]), int(r[1]))
+        print("  env %4d step %4d %s switch margin %.3g m, narrow-phase residual %.2g: %d entries outside, worst error %.3g%s" % (k[0], k[1], "deep" if r[3] else "well", r[2], r[7], r[5], r[6],
+              " | the oracle's own step from the fp32-rounded state differs by %.3g" % sens[k] if k in sens else ""))
+
+
+if "--variant" in sys.argv:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--variant", choices=["pair", "pair_lean"], required=True)
+    ap.add_argument("--inputs", choices=["augmented", "mass", "thread"], default="mass")
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--seed", type=int, default=4)
+    ap.add_argument("--task", default="move_to_pose")
+    ap.add_argument("--flat-out", action="store_true")
+    ap.add_argument("--skip", type=int, default=0)
+    ap.add_argument("--deep-only", action="store_true")
+    ap.add_argument("--sensitivity", action="store_true")
+    pair(ap.parse_args())
+else:
+    nominal(int(sys.argv[1]) if len(sys.argv) > 1 else 64, int(sys.argv[2]) if len(sys.argv) > 2 else 100, sys.argv[3] if len(sys.argv) > 3 else "move_from_origin")

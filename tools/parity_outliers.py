@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from jitterbug_amd import model
 from jitterbug_amd.vec_env import JitterbugVecEnv
 from oracle import oracle as O
+from tests.test_gpu_parity import MARGIN_TOL
 task, n, steps, seed = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
 flat_out = len(sys.argv) > 5 and sys.argv[5] == "flat"
 skip = int(sys.argv[6]) if len(sys.argv) > 6 else 0
@@ -27,7 +28,7 @@ for t in range(-skip, steps):
     og, rg, dg, _ = g.step(a)
     capd = g.counters()[2] - cap0
     oo, ro, do = o.step(a, auto_reset=False)
-    well = o.margins() >= 3e-8
+    well = o.margins() >= MARGIN_TOL
     og = og.astype(np.float64)
     err = np.abs(og - oo)
     bad = (err > 1e-4 * np.abs(oo) + 1e-6) & well[:, None]
