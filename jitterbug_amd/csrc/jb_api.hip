@@ -17,6 +17,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/jitterbug_hip.h"
@@ -29,6 +30,7 @@
 #include "jb_sim.hpp"
 #include "jb_step.hpp"
 #include "jb_task.hpp"
+#include "jb_variant.hpp"
 #include "jb_witness.hpp"
 
 using namespace jb;
@@ -39,7 +41,6 @@ using namespace jb;
 
 namespace {
 
-constexpr int OVC_FLOATS_PER_LANE = 4 * (NSLOT - ROW_K) + 9;      // LEAN kernels' per-wave block in global memory: overflow candidates + the second pair contact's frame
 enum RootF : int { RF_P = 0, RF_Q = 3, RF_V = 7, RF_W = 10, RF_PHI = 13, RF_PHID = 14, RF_TURNS = 15, RF_WA = 16, RF_WL = 19, RF_WM = 22, RF_FAIL = 23, RF_TGT = 24, RF_LO = 27 /*5: low-order words of z and the quaternion*/, ROOT_F = 32 };
 enum LegF : int { LF_TH1 = 0, LF_TH2 = 1, LF_THD1 = 2, LF_THD2 = 3, LF_WJ0 = 4, LF_WJ1 = 5, LEG_F = 6 };
 
@@ -231,8 +232,9 @@ __device__ __forceinline__ void step_body(KArgs a, StepIO io) {
     // Lanes 0 .. 4*EPW-1 are the MAIN lanes (quad q = env q of this wave, lane = leg).  A wave with fewer than 16 envs uses
     // its spare lanes as NGRP-1 helper groups: helper lane L + g*4*EPW mirrors main lane L (same env, leg, scratch and
     // constant-table addresses) and takes a share of the live contact slots in every Newton pass (jb_sim.hpp, SlotPlan).
-    constexpr int MAIN = 4 * EPW;
-    constexpr int NGRP = EPW == 8 ? 2 : 4;
+    constexpr StepLayout LAY = step_layout(EPW, LEAN, PAIR);      // jb_variant.hpp: the one description of this variant
+    constexpr int MAIN = LAY.main_lanes;
+    constexpr int NGRP = LAY.groups;
     static_assert(EPW == 1 || EPW == 2 || EPW == 4 || EPW == 8, "envs per wave");
     const int lane_in_grp = threadIdx.x % MAIN, grp = threadIdx.x / MAIN;
     const int quad = lane_in_grp >> 2, leg = threadIdx.x & 3;
@@ -247,12 +249,12 @@ __device__ __forceinline__ void step_body(KArgs a, StepIO io) {
     const int env = lblock * EPW + quad;
     const unsigned long long clock0 = __builtin_amdgcn_s_memrealtime();
     LaneModel<float> m;
-    constexpr int SCN = LEAN ? (PAIR ? SC_COUNT_LEAN_PAIR : SC_COUNT_LEAN) : SC_COUNT;      // floats of per-lane scratch
+    constexpr int SCN = LAY.scratch_floats;      // floats of per-lane scratch
     // AUX bodies (jb_sim.hpp SimOpts::aux): the ordinary kernel with four lane groups and a shared model - groups 2 and 3 run phase A on the
     // motor body and the root body's own mass instead of idling while every leg lane repeats that work
-    constexpr bool AUX = !LEAN && !PAIR && NGRP == 4;
+    constexpr bool AUX = LAY.aux;
     constexpr bool aux_on = AUX;
-    stage_model<LEAN && PAIR>(a, lds + SCN * 4 * EPW, lblock, quad, leg, m, LEAN, PAIR || !LEAN, aux_on ? grp : -1);      // (LEAN + PAIR is only launched with one model per env: split tables)
+    stage_model<LAY.split_tables>(a, lds + SCN * MAIN, lblock, quad, leg, m, LEAN, LAY.pair_entries, aux_on ? grp : -1);      // (LEAN + PAIR is only launched with one model per env: split tables)
     if (grp >= NGRP || env >= a.n) return;       // whole quads (and their mirrors in every group) retire together
     const int lane = env * 4 + leg;
     LaneScratch<float> scr;
@@ -260,16 +262,17 @@ __device__ __forceinline__ void step_body(KArgs a, StepIO io) {
     scr.stride = MAIN;
     scr.grp = grp; scr.ngrp = NGRP; scr.gstride = MAIN;
     // (LEAN: per wave a block in global memory - the overflow candidates, then the second pair contact's frame: rare paths both)
-    if (LEAN) { scr.ovc = a.ovc_buf + (size_t)lblock * (OVC_FLOATS_PER_LANE * MAIN) + lane_in_grp; scr.pd2 = 4 * (NSLOT - ROW_K); scr.red_lds = false; }
-    else { scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = SC_PD2 - SC_OVC; scr.red_lds = true; }
+    static_assert(LAY.lean == LEAN && LAY.red_lds == !LEAN && (LAY.ovc_floats != 0) == LEAN, "the LEAN layout: no reduction hand-over, overflow block in global memory");
+    if (LEAN) { scr.ovc = a.ovc_buf + (size_t)lblock * (LAY.ovc_floats * MAIN) + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds; }
+    else { scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds; }
     scr.ovc_stride = MAIN;
-    scr.pd = LEAN ? SC_PD_LEAN : SC_PD;
+    scr.pd = LAY.pd;
     scr.aux_lane = aux_on && grp >= 2;
 #ifdef JB_WAVE_STATS
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
 #endif
     LaneState<float> s;
-    constexpr bool OFFLOAD = !LEAN;              // lane group 1 replicates the main lanes (jb_sim.hpp SimOpts::offload)
+    constexpr bool OFFLOAD = LAY.offload;         // lane group 1 replicates the main lanes (jb_sim.hpp SimOpts::offload)
     // the lanes that hold an env's state: the main lanes, their replica and the aux lanes.  All run everything below that changes the state
     // (substeps, failure flag, episode reset) with the very same instructions; only the main lanes write to memory.
     const bool rep = grp == 0 || (OFFLOAD && grp == 1) || scr.aux_lane;
@@ -854,21 +857,34 @@ struct HipDeviceApi {
 
 static dim3 grid_lanes(int n) { return dim3((unsigned)(((size_t)n * 4 + 63) / 64)); }
 
-// Which step kernel a handle runs.  JB_FLAG_LEAN is honoured where a LEAN instantiation exists: a shared model without the pair contact
-// (envs per wave 1, 2 or 4), or one model per env at four envs per wave (LEAN + PAIR, split tables).  Anything else that asks for LEAN is
-// refused (JB_E_INVALID) at the call that creates the combination - never silently run as the ordinary kernel.
-static int kernel_variant(const KArgs& k) {
-    if (k.lean && k.pair && k.per_env_model && k.epw == 4) return JB_VARIANT_LEAN_PAIR;
-    if (k.pair) return JB_VARIANT_PAIR;
-    if (k.lean) return JB_VARIANT_LEAN;
-    return JB_VARIANT_ORDINARY;
+// Which step kernel a handle runs: the row of jb_variant.hpp's launchable set for (LEAN, PAIR, one model per env, envs per wave).  A
+// combination without a row is refused (JB_E_INVALID) at the call that creates it - never silently run as another kernel.
+typedef void (*StepKernel)(KArgs, StepIO);
+template <int I> static StepKernel step_row_kernel() {
+    constexpr StepRow r = STEP_ROWS[I];
+#ifdef JB_DEV_ONLY4      // development builds: the one instantiation the headline runs (a fifth of the compile time)
+    constexpr bool built = r.variant == JB_VARIANT_ORDINARY && r.epw == 4;
+#else
+    constexpr bool built = true;
+#endif
+    if constexpr (!built) return nullptr;
+    else if constexpr (r.lean && r.pair) return jb_step_kernel_lean_pair<r.epw>;
+    else if constexpr (r.pair) return jb_step_kernel_pair<r.epw>;
+    else if constexpr (r.lean) return jb_step_kernel_lean<r.epw>;
+    else return jb_step_kernel<r.epw>;
 }
+template <int... I> static const StepKernel* step_kernels(std::integer_sequence<int, I...>) {
+    static const StepKernel table[] = {step_row_kernel<I>()...};      // by row of STEP_ROWS
+    return table;
+}
+static int kernel_variant(const KArgs& k) { return step_variant(k.lean, k.pair, k.per_env_model, k.epw); }
 static int check_variant(int lean, int pair, int per_env_model, int epw) {
-    if (lean && pair && !(per_env_model && epw == 4))
+    if (step_row(lean, pair, per_env_model, epw) != STEP_NOT_LAUNCHABLE) return JB_OK;
+    if (lean && pair)
         return fail(JB_E_INVALID, "JB_FLAG_LEAN cannot be honoured: the pair-contact kernel has a two-waves-per-SIMD form only for one model per env at 4 envs per wave "
                                   "(this handle: " + std::string(per_env_model ? "one model per env" : "a shared model that needs the pair contact") + ", " + std::to_string(epw) +
                                   " envs per wave); drop JB_FLAG_LEAN, or add JB_FLAG_NO_PAIR for floor contacts only");
-    return JB_OK;
+    return fail(JB_E_INVALID, "no step kernel for " + std::to_string(epw) + " envs per wave" + (lean ? " with JB_FLAG_LEAN" : ""));
 }
 // The one way a model becomes the handle's (jb_create, jb_set_model_params, jb_randomise_models): `fresh`, when not empty, replaces the
 // table buffer (empty: the tables were rewritten in place), and the kernel arguments follow.  The caller has synchronised the stream.
@@ -1128,7 +1144,11 @@ static int launch_step(jb_handle* h, StepIO io, int packed_rows) {
     if (io.n_steps < 1) return fail(JB_E_INVALID, "n_steps must be >= 1");
     if (!io.use_policy && !io.actions) return fail(JB_E_INVALID, "action buffer is NULL");
     JB_ENTER(h);
-    { int rc = check_variant(h->ka.lean, h->ka.pair, h->ka.per_env_model, h->ka.epw); if (rc) return rc; }
+    const int row = step_row(h->ka.lean, h->ka.pair, h->ka.per_env_model, h->ka.epw);
+    if (row == STEP_NOT_LAUNCHABLE) return check_variant(h->ka.lean, h->ka.pair, h->ka.per_env_model, h->ka.epw);
+    const StepKernel kernel = step_kernels(std::make_integer_sequence<int, N_STEP_ROWS>())[row];
+    if (!kernel) return fail(JB_E_INVALID, "JB_DEV_ONLY4 build: only the ordinary kernel at 4 envs per wave");
+    const StepLayout lay = step_layout(h->ka.epw, STEP_ROWS[row].lean, STEP_ROWS[row].pair);
     RoctxRange range(io.n_steps > 1 ? "jb_step_many" : "jb_step");
     h->ka.packed_rows = packed_rows;
     io.pp = h->policy;
@@ -1140,80 +1160,39 @@ static int launch_step(jb_handle* h, StepIO io, int packed_rows) {
         h->d_wave_clock = std::move(clock);
     }
     io.wave_clock = h->d_wave_clock.get();
-    const int variant = kernel_variant(h->ka);
     // more waves than the device holds at once -> launch them longest first (the order comes from the previous launch's clocks)
-    bool reorder = false;
-    int fold_from = 0;
+    WaveOrderPlan order_plan = {false, 0};
     if (!(h->cfg.flags & JB_FLAG_NO_REORDER)) {
         if (h->wave_slots == 0) {
             hipDeviceProp_t prop;
             JB_HIP(hipGetDeviceProperties(&prop, h->cfg.device_id));
             h->wave_slots = prop.multiProcessorCount * 4;
         }
-        const int per_simd_x2 = (variant == JB_VARIANT_LEAN || variant == JB_VARIANT_LEAN_PAIR) ? 4 : 2;      // resident waves per SIMD, times two
-        reorder = (long long)grid.x * 2 > (long long)h->wave_slots * per_simd_x2;
-        // two waves per SIMD and the whole batch resident: no launch ORDER to choose, but who shares a SIMD with whom (jb_wave_order_kernel)
-        if (per_simd_x2 == 4 && (int)grid.x > h->wave_slots && !reorder) { reorder = true; fold_from = h->wave_slots; }
-        if (reorder && !h->d_wave_order) {
+        order_plan = wave_order_plan((int)grid.x, h->wave_slots, lay.waves_per_simd);
+        if (order_plan.reorder && !h->d_wave_order) {
             Dev<int> order;
             JB_HIP(order.alloc((size_t)h->cfg.n_envs));
-            hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock.get(), order.get(), (int)grid.x, fold_from);      // (clocks all zero: identity)
+            hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock.get(), order.get(), (int)grid.x, order_plan.fold_from);      // (clocks all zero: identity)
             JB_HIP(hipGetLastError());
             h->d_wave_order = std::move(order);
         }
     }
-    io.wave_order = reorder ? h->d_wave_order.get() : nullptr;
-    const bool lean_pair = variant == JB_VARIANT_LEAN_PAIR, use_lean = lean_pair || variant == JB_VARIANT_LEAN;
-    const bool aux_bodies = variant == JB_VARIANT_ORDINARY && h->ka.epw <= 4;      // (step_body: AUX - an aux block behind every staged table)
-    const size_t lds_bytes = lean_pair ? ((size_t)SC_COUNT_LEAN_PAIR * 4 * h->ka.epw + (size_t)LM_SPLIT_RES * h->ka.epw) * sizeof(float)
-                                       : ((size_t)(use_lean ? SC_COUNT_LEAN : SC_COUNT) * 4 * h->ka.epw + ((size_t)(use_lean ? LM_TABLE_BASE : LM_TABLE) + (aux_bodies ? LM_AUX : 0)) * (h->ka.per_env_model ? h->ka.epw : 1)) * sizeof(float);
+    io.wave_order = order_plan.reorder ? h->d_wave_order.get() : nullptr;
+    const size_t lds_bytes = step_lds_bytes(lay, h->ka.per_env_model != 0);
 #ifdef JB_DEBUG
     static const size_t extra_lds = getenv("JB_DEBUG_EXTRA_LDS") ? (size_t)atoi(getenv("JB_DEBUG_EXTRA_LDS")) : 0;      // occupancy experiments (-DJB_DEBUG builds only)
     const size_t lds_bytes_x = lds_bytes + extra_lds;
 #else
     const size_t lds_bytes_x = lds_bytes;
 #endif
-    if (use_lean && !h->d_ovc) {      // the LEAN variant's overflow candidates (beyond the row cache): one block per wave
-        JB_HIP(h->d_ovc.alloc((size_t)grid.x * OVC_FLOATS_PER_LANE * 4 * h->ka.epw));      // (a failed allocation leaves it empty)
+    if (lay.ovc_floats && !h->d_ovc) {      // the LEAN variants' block per wave: overflow candidates (beyond the row cache), the second pair contact's frame
+        JB_HIP(h->d_ovc.alloc((size_t)grid.x * lay.ovc_floats * lay.main_lanes));      // (a failed allocation leaves it empty)
         h->ka.ovc_buf = h->d_ovc.get();
     }
-#define JB_LAUNCH_STEP(E) hipLaunchKernelGGL(jb_step_kernel<E>, grid, dim3(64), lds_bytes_x, h->stream, h->ka, io)
-#define JB_LAUNCH_LEAN(E) hipLaunchKernelGGL(jb_step_kernel_lean<E>, grid, dim3(64), lds_bytes_x, h->stream, h->ka, io)
-#define JB_LAUNCH_PAIR(E) hipLaunchKernelGGL(jb_step_kernel_pair<E>, grid, dim3(64), lds_bytes_x, h->stream, h->ka, io)
-#ifdef JB_DEV_ONLY4      // development builds: the one instantiation the headline runs (a fifth of the compile time)
-    if (variant != JB_VARIANT_ORDINARY || h->ka.epw != 4) return fail(JB_E_INVALID, "JB_DEV_ONLY4 build: only the ordinary kernel at 4 envs per wave");
-    JB_LAUNCH_STEP(4);
-#else
-    if (lean_pair) {
-        hipLaunchKernelGGL(jb_step_kernel_lean_pair<4>, grid, dim3(64), lds_bytes_x, h->stream, h->ka, io);
-    } else if (variant == JB_VARIANT_PAIR) {
-        switch (h->ka.epw) {
-        case 1: JB_LAUNCH_PAIR(1); break;
-        case 2: JB_LAUNCH_PAIR(2); break;
-        case 4: JB_LAUNCH_PAIR(4); break;
-        default: JB_LAUNCH_PAIR(8); break;
-        }
-    } else if (use_lean) {
-        switch (h->ka.epw) {
-        case 1: JB_LAUNCH_LEAN(1); break;
-        case 2: JB_LAUNCH_LEAN(2); break;
-        default: JB_LAUNCH_LEAN(4); break;
-        }
-    } else {
-        switch (h->ka.epw) {
-        case 1: JB_LAUNCH_STEP(1); break;
-        case 2: JB_LAUNCH_STEP(2); break;
-        case 4: JB_LAUNCH_STEP(4); break;
-        default: JB_LAUNCH_STEP(8); break;
-        }
-    }
-#endif
-#undef JB_LAUNCH_STEP
-#undef JB_LAUNCH_LEAN
-#undef JB_LAUNCH_PAIR
+    hipLaunchKernelGGL(kernel, grid, dim3(64), lds_bytes_x, h->stream, h->ka, io);
     JB_HIP(hipGetLastError());
-    if (reorder) {
-        hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock.get(), h->d_wave_order.get(), (int)grid.x, fold_from);
+    if (order_plan.reorder) {
+        hipLaunchKernelGGL(jb_wave_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_wave_clock.get(), h->d_wave_order.get(), (int)grid.x, order_plan.fold_from);
         JB_HIP(hipGetLastError());
     }
     if (h->cfg.flags & JB_FLAG_PAIR_WITNESS) {      // one witness pass behind every step launch (the state the launch left)

@@ -9,25 +9,23 @@
 
 #include "../jitterbug_amd/csrc/jb_model_build.hpp"
 #include "../jitterbug_amd/csrc/jb_step.hpp"
+#include "../jitterbug_amd/csrc/jb_variant.hpp"
 
 using namespace jb;
 
-// NGROUPS = 1: the main lanes alone.  NGROUPS = 4: the wave layout of the 4-envs-per-wave kernel for ONE env - a main group and three
-// helper groups, one host thread each, sharing the scratch and exchanging through jb_lane.hpp's HostWave (group_sum, row_transpose_sum,
-// the rank-one pass on rows other groups built, the broadcast loop decisions): the same code paths the device takes with helper lanes.
+// ngroups = 4: the wave layout of the 4-envs-per-wave kernel for ONE env - a main group and three helper groups, one host thread each,
+// sharing the scratch and exchanging through jb_lane.hpp's HostWave (group_sum, row_transpose_sum, the rank-one pass on rows other groups
+// built, the broadcast loop decisions): the same code paths the device takes with helper lanes.  ngroups = 2: the 8-envs-per-wave kernel's
+// two groups.  ngroups = 1: the main lanes alone (the harness's own diagnostic shape).  The layout itself is jb_variant.hpp's.
 static int g_offload = 1;      // lane group 1 as the main lanes' replica (SimOpts::offload), as the one-wave-per-SIMD kernels run it
 extern "C" void jbh_set_offload(int on) { g_offload = on; }
 static int g_aux = 1;          // aux bodies on lane groups 2 / 3 (SimOpts::aux)
 extern "C" void jbh_set_aux(int on) { g_aux = on; }
 static int g_spread = 1;       // spread contact sweeps (SimOpts::spread)
 extern "C" void jbh_set_spread(int on) { g_spread = on; }
-template <typename T>
-static int run(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int implicit_damp, double* fail, int ngroups = 1, int rank_one = 1, int lean = 0, int pair = 0) {
+
+template <typename T> static LaneState<Quad<T>> state_from_qpos(const double* qpos, const double* qvel) {
     using V = Quad<T>;
-    LaneModel<V> m;
-    T tab[LM_TABLE];
-    { int rc = build_packed_model<T>(P, tab); if (rc) return rc; }
-    m.c.inv = tab; m.c.tab = tab + LM_INV; m.c.lean = lean != 0; m.c.preload();
     LaneState<V> s;
     s.px = V(T(qpos[0])); s.py = V(T(qpos[1])); s.pz = V(T(qpos[2]));
     s.qw = V(T(qpos[3])); s.qx = V(T(qpos[4])); s.qy = V(T(qpos[5])); s.qz = V(T(qpos[6]));
@@ -44,70 +42,9 @@ static int run(const double* P, double* qpos, double* qvel, double ctrl, int nsu
     s.thd2 = V(T(qvel[7]), T(qvel[9]), T(qvel[11]), T(qvel[13]));
     for (int i = 0; i < 3; i++) { s.wa[i] = V(T(0)); s.wl[i] = V(T(0)); }
     s.wj[0] = s.wj[1] = V(T(0)); s.wm = V(T(0)); s.fail = V(T(0));
-    SimOpts o; o.contacts = contacts; o.max_newton = max_newton; o.implicit_damp = implicit_damp; o.rank_one = rank_one; o.lean = lean; o.offload = (g_offload && !lean && ngroups >= 2) ? 1 : 0; o.prof = nullptr; o.hist = nullptr;
-    o.spread = g_spread;
-    o.aux = (g_aux && o.offload && ngroups == 4 && !pair) ? 1 : 0;          // groups 2 and 3 run phase A on the motor body and the root body (SimOpts::aux), like the ordinary device kernel
-    T auxtab[LM_AUX];
-    build_aux_block<T>(tab, auxtab);
-    LaneModel<V> m_aux = m;
-    m_aux.c.tab = auxtab; m_aux.c.tab_rare = tab + LM_INV; m_aux.c.preload();
-    constexpr int SCMAX = SC_COUNT > SC_COUNT_LEAN_PAIR ? SC_COUNT : SC_COUNT_LEAN_PAIR;
-    V scratch[SCMAX];                  // (the LEAN variant parks state / system / factorisation where the ordinary one has its reduction buffer and overflow candidates)
-    V ovcbuf[4 * (NSLOT - ROW_K) + 9]; // LEAN: the candidates beyond the row cache live outside the scratch (global memory on the device), and behind them the thread pair contact's frame
-    auto set_ovc = [&](LaneScratch<V>& sc) {
-        sc.ovc = lean ? ovcbuf : scratch + SC_OVC; sc.ovc_stride = 1; sc.red_lds = !lean; sc.pd = lean ? SC_PD_LEAN : SC_PD;
-        sc.pd2 = lean ? 4 * (NSLOT - ROW_K) : SC_PD2 - SC_OVC;
-    };
-    normalise_state(s);
-    if (ngroups <= 1) {
-        LaneScratch<V> sc; sc.p = scratch; sc.stride = 1; sc.grp = 0; sc.ngrp = 1; sc.gstride = 4; set_ovc(sc);
-        for (int k = 0; k < SCMAX; k++) scratch[k] = V(std::numeric_limits<T>::quiet_NaN());
-        if (lean) state_store(sc, s);
-        scratch[sc.pd + 11] = V(T(0));         // the narrow phase starts cold in every control step
-        for (int i = 0; i < nsub; i++) {
-            // poison the scratch: a substep must not read anything it has not written itself (on the device LDS keeps whatever
-            // the previous kernel left there); in the LEAN variant the parked state is the one thing that carries over
-            for (int k = 0; k < (lean ? SC_LSTATE : SCMAX); k++) if (k < sc.pd + 9 || k > sc.pd + 11) scratch[k] = V(std::numeric_limits<T>::quiet_NaN());      // (the pair's warm start carries over, like on the device)
-            for (auto& c : ovcbuf) c = V(std::numeric_limits<T>::quiet_NaN());
-            if (pair) substep<V, true>(m, sc, s, V(T(ctrl)), o); else substep<V>(m, sc, s, V(T(ctrl)), o);
-        }
-        if (lean) state_load(sc, s);
-    } else {
-        HostWave wave;
-        wave.ngrp = ngroups; wave.gstride = ngroups == 2 ? 32 : 16;            // 16: the lane distance between groups in the 4-envs-per-wave kernel (selects its transposed reduction); 32: the 8-envs-per-wave kernel's two groups
-        auto body = [&](int g) {
-            g_host_wave = &wave; g_host_grp = g;
-            LaneScratch<V> sc; sc.p = scratch; sc.stride = 1; sc.grp = g; sc.ngrp = ngroups; sc.gstride = ngroups == 2 ? 32 : 16; set_ovc(sc);
-            sc.aux_lane = o.aux && g >= 2;
-            const LaneModel<V>& mg = sc.aux_lane ? m_aux : m;
-            LaneState<V> hs = s;                            // helper lanes start from a harmless state, like the kernel's (replica and aux lanes: from the env's state)
-            LaneState<V>& st = (g == 0) ? s : hs;
-            if (g != 0 && !(o.offload && g == 1) && !sc.aux_lane) {
-                hs.px = hs.py = hs.pz = V(T(0)); hs.qw = V(T(1)); hs.qx = hs.qy = hs.qz = V(T(0)); hs.vx = hs.vy = hs.vz = hs.wx = hs.wy = hs.wz = V(T(0));
-                hs.pz_lo = hs.qw_lo = hs.qx_lo = hs.qy_lo = hs.qz_lo = V(T(0));
-                hs.phi = hs.phid = hs.turns = V(T(0)); hs.th1 = hs.th2 = hs.thd1 = hs.thd2 = V(T(0));
-            }
-            if (g == 0) {
-                for (int k = 0; k < SCMAX; k++) scratch[k] = V(std::numeric_limits<T>::quiet_NaN());
-                if (lean) state_store(sc, st);
-                if (o.offload) for (int k = 0; k < 56; k++) scratch[SC_ZERO + k] = V(T(0));       // written once per kernel on the device
-            }
-            for (int i = 0; i < nsub; i++) {
-                wave.barrier();
-                if (g == 0) { for (int k = 0; k < (lean ? SC_LSTATE : o.offload ? SC_ZERO : SCMAX); k++) if (i == 0 || k < sc.pd + 9 || k > sc.pd + 11) scratch[k] = V(std::numeric_limits<T>::quiet_NaN()); if (i == 0) scratch[sc.pd + 11] = V(T(0)); for (auto& c : ovcbuf) c = V(std::numeric_limits<T>::quiet_NaN()); }
-                wave.barrier();
-                if (pair) substep<V, true>(mg, sc, st, V(T(ctrl)), o); else substep<V>(mg, sc, st, V(T(ctrl)), o);
-            }
-            if (g == 0 && lean) state_load(sc, st);
-            g_host_wave = nullptr;
-        };
-        std::vector<std::thread> th;
-        for (int g = 1; g < ngroups; g++) th.emplace_back(body, g);
-        body(0);
-        for (auto& t : th) t.join();
-    }
-    // replicated quantities must agree across the quad
-    for (int l = 1; l < 4; l++) if (s.px.v[l] != s.px.v[0] || s.qw.v[l] != s.qw.v[0] || s.wz.v[l] != s.wz.v[0] || s.phid.v[l] != s.phid.v[0]) return -100;
+    return s;
+}
+template <typename T> static void qpos_from_state(const LaneState<Quad<T>>& s, double* qpos, double* qvel) {
     T n = std::sqrt(s.qw.v[0] * s.qw.v[0] + s.qx.v[0] * s.qx.v[0] + s.qy.v[0] * s.qy.v[0] + s.qz.v[0] * s.qz.v[0]);
     qpos[0] = s.px.v[0]; qpos[1] = s.py.v[0]; qpos[2] = (double)s.pz.v[0] + (double)s.pz_lo.v[0];
     qpos[3] = ((double)s.qw.v[0] + (double)s.qw_lo.v[0]) / n; qpos[4] = ((double)s.qx.v[0] + (double)s.qx_lo.v[0]) / n;
@@ -115,38 +52,123 @@ static int run(const double* P, double* qpos, double* qvel, double ctrl, int nsu
     qvel[0] = s.vx.v[0]; qvel[1] = s.vy.v[0]; qvel[2] = s.vz.v[0]; qvel[3] = s.wx.v[0]; qvel[4] = s.wy.v[0]; qvel[5] = s.wz.v[0];
     for (int l = 0; l < 4; l++) { qpos[7 + 2 * l] = s.th1.v[l]; qpos[8 + 2 * l] = s.th2.v[l]; qvel[6 + 2 * l] = s.thd1.v[l]; qvel[7 + 2 * l] = s.thd2.v[l]; }
     qpos[15] = (double)s.phi.v[0] + 2 * M_PI * (double)s.turns.v[0]; qvel[14] = s.phid.v[0];
+}
+
+// One env's share of a wave on the host: the model (and its aux twin), the scratch, and one host thread per lane group.
+template <typename T> struct HostRun {
+    using V = Quad<T>;
+    StepLayout lay;                    // the wave this run stands for, with the harness's overrides (ngroups, g_offload, g_aux) on top
+    SimOpts o;
+    T tab[LM_TABLE], auxtab[LM_AUX];
+    LaneModel<V> m, m_aux;
+    V scratch[SC_COUNT];               // (the LEAN variants park state / system / factorisation where the ordinary one has its reduction buffer and overflow candidates)
+    V ovcbuf[OVC_FLOATS_PER_LANE];     // LEAN: the candidates beyond the row cache live outside the scratch (global memory on the device), and behind them the thread pair contact's frame
+    HostWave wave;
+    static_assert(SC_COUNT >= SC_COUNT_LEAN_PAIR && SC_COUNT >= SC_COUNT_LEAN, "the scratch holds every variant's");
+    struct Group { int g; LaneScratch<V> sc; const LaneModel<V>* m; bool rep; LaneState<V> s; };      // rep: the lanes that hold the env's state (main, replica, aux)
+
+    int init(const double* P, int ngroups, bool lean, bool pair, int contacts, int max_newton, int implicit_damp, int rank_one) {
+        if (int rc = build_packed_model<T>(P, tab)) return rc;
+        m.c.inv = tab; m.c.tab = tab + LM_INV; m.c.lean = lean; m.c.preload();
+        build_aux_block<T>(tab, auxtab);
+        m_aux = m;
+        m_aux.c.tab = auxtab; m_aux.c.tab_rare = tab + LM_INV; m_aux.c.preload();
+        lay = step_layout(ngroups == 2 ? 8 : 4, lean, pair);
+        lay.groups = ngroups;
+        lay.offload = lay.offload && g_offload && ngroups >= 2;
+        lay.aux = lay.aux && g_aux && lay.offload;          // (rides on the replica's layout)
+        o = sim_opts(lay, contacts, max_newton, implicit_damp, rank_one, g_spread);
+        wave.ngrp = ngroups; wave.gstride = lay.main_lanes;      // the lane distance between groups selects the reduction (16: the 4-envs-per-wave kernel's transposed one)
+        return 0;
+    }
+    void sync() { if (lay.groups > 1) wave.barrier(); }
+    void poison(int count) { for (int k = 0; k < count; k++) scratch[k] = V(std::numeric_limits<T>::quiet_NaN()); }
+    // Every lane group runs body(Group&) from the env's state s0 (helper lanes: from a harmless one), group 0 on the caller's thread.
+    template <typename F> void run(const LaneState<V>& s0, F body) {
+        auto group = [&](int g) {
+            if (lay.groups > 1) { g_host_wave = &wave; g_host_grp = g; }
+            Group G;
+            G.g = g;
+            bind_scratch(G.sc, lay, scratch, 1, g, ovcbuf);
+            G.m = G.sc.aux_lane ? &m_aux : &m;
+            G.rep = holds_state(lay, g);
+            G.s = s0;
+            if (!G.rep) helper_lane_state(G.s);
+            if (g == 0) {
+                poison(SC_COUNT);
+                if (lay.offload) for (int k = 0; k < 56; k++) scratch[SC_ZERO + k] = V(T(0));       // written once per kernel on the device
+            }
+            body(G);
+            g_host_wave = nullptr;
+        };
+        std::vector<std::thread> th;
+        for (int g = 1; g < lay.groups; g++) th.emplace_back(group, g);
+        group(0);
+        for (auto& t : th) t.join();
+    }
+    // Before every substep: poison the scratch - a substep must not read anything it has not written itself (on the device LDS keeps whatever
+    // the previous kernel left there).  What carries over: the replica's zeros and, in the LEAN variants, the parked state.  pair_warm_start (the
+    // entry points that may run the PAIR substep): the pair narrow phase's warm start too, within a control step - it starts cold in every one.
+    // Without it those three slots are poisoned like the rest: a substep without the pair contact must not read them.
+    void before_substep(const Group& G, bool pair_warm_start, bool first_of_control_step) {
+        sync();
+        if (G.g == 0) {
+            const int pd = G.sc.pd;
+            const bool keep = pair_warm_start && !first_of_control_step;
+            for (int k = 0; k < (lay.lean ? SC_LSTATE : lay.offload ? SC_ZERO : SC_COUNT); k++) if (!keep || k < pd + 9 || k > pd + 11) scratch[k] = V(std::numeric_limits<T>::quiet_NaN());
+            if (pair_warm_start && first_of_control_step) scratch[pd + 11] = V(T(0));
+            for (auto& c : ovcbuf) c = V(std::numeric_limits<T>::quiet_NaN());
+        }
+        sync();
+    }
+};
+
+template <typename T>
+static int run(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int implicit_damp, double* fail, int ngroups, int rank_one, int lean, int pair) {
+    using V = Quad<T>;
+    HostRun<T> w;
+    if (int rc = w.init(P, ngroups, lean != 0, pair != 0, contacts, max_newton, implicit_damp, rank_one)) return rc;
+    LaneState<V> s = state_from_qpos<T>(qpos, qvel);
+    normalise_state(s);
+    w.run(s, [&](typename HostRun<T>::Group& G) {
+        if (G.g == 0 && lean) state_store(G.sc, G.s);
+        for (int i = 0; i < nsub; i++) {
+            w.before_substep(G, true, i == 0);
+            if (pair) substep<V, true>(*G.m, G.sc, G.s, V(T(ctrl)), w.o); else substep<V>(*G.m, G.sc, G.s, V(T(ctrl)), w.o);
+        }
+        if (G.g == 0) { if (lean) state_load(G.sc, G.s); s = G.s; }
+    });
+    // replicated quantities must agree across the quad
+    for (int l = 1; l < 4; l++) if (s.px.v[l] != s.px.v[0] || s.qw.v[l] != s.qw.v[0] || s.wz.v[l] != s.wz.v[0] || s.phid.v[l] != s.phid.v[0]) return -100;
+    qpos_from_state<T>(s, qpos, qvel);
     if (fail) *fail = s.fail.v[0];
     return 0;
 }
 
-extern "C" int jbh_step(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int implicit_damp,
-                        int use_float, double* fail) {
-    return use_float ? run<float>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, implicit_damp, fail)
-                     : run<double>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, implicit_damp, fail);
-}
-// the same with ngroups lane groups (1 or 4) and the rank-one Newton passes on or off
-extern "C" int jbh_step_groups(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int use_float, int ngroups, int rank_one, double* fail) {
+// fp32 or fp64, with ngroups lane groups (1, 2 or 4)
+static int run_as(int use_float, const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int implicit_damp, double* fail, int ngroups = 1, int rank_one = 1, int lean = 0, int pair = 0) {
     if (ngroups != 1 && ngroups != 2 && ngroups != 4) return -101;
-    return use_float ? run<float>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one)
-                     : run<double>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one);
+    return use_float ? run<float>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, implicit_damp, fail, ngroups, rank_one, lean, pair)
+                     : run<double>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, implicit_damp, fail, ngroups, rank_one, lean, pair);
+}
+extern "C" int jbh_step(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int implicit_damp, int use_float, double* fail) {
+    return run_as(use_float, P, qpos, qvel, ctrl, nsub, contacts, max_newton, implicit_damp, fail);
+}
+// the same with ngroups lane groups and the rank-one Newton passes on or off
+extern "C" int jbh_step_groups(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int use_float, int ngroups, int rank_one, double* fail) {
+    return run_as(use_float, P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one);
 }
 // ... and in the LEAN variant (state / system / factorisation parked in the scratch, constants never preloaded)
 extern "C" int jbh_step_lean(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int use_float, int ngroups, int rank_one, double* fail) {
-    if (ngroups != 1 && ngroups != 2 && ngroups != 4) return -101;
-    return use_float ? run<float>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 1)
-                     : run<double>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 1);
+    return run_as(use_float, P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 1);
 }
 // ... and with the geom-geom pair contact (mass ellipsoid against the upper-leg cylinders): the PAIR instantiation of the substep
 extern "C" int jbh_step_pair(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int use_float, int ngroups, int rank_one, double* fail) {
-    if (ngroups != 1 && ngroups != 2 && ngroups != 4) return -101;
-    return use_float ? run<float>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 0, 1)
-                     : run<double>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 0, 1);
+    return run_as(use_float, P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 0, 1);
 }
 // ... and PAIR in the LEAN layout (parked state / system / factorisation incl. the cross term's share, pair frame behind them)
 extern "C" int jbh_step_pair_lean(const double* P, double* qpos, double* qvel, double ctrl, int nsub, int contacts, int max_newton, int use_float, int ngroups, int rank_one, double* fail) {
-    if (ngroups != 1 && ngroups != 2 && ngroups != 4) return -101;
-    return use_float ? run<float>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 1, 1)
-                     : run<double>(P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 1, 1);
+    return run_as(use_float, P, qpos, qvel, ctrl, nsub, contacts, max_newton, 1, fail, ngroups, rank_one, 1, 1);
 }
 // ---- K control steps in ONE call, the loop of the fused rollout kernel (jb_api.hip step_body): the state, the step counter, the episode
 // number and the target stay in the lane variables between the control steps; every step = normalise + nsub substeps +
@@ -157,61 +179,21 @@ template <typename T>
 static int rollout(const double* P, double* qpos, double* qvel, double* target, int* counters, int K, const double* actions, int task, int nsub, int step_limit, int auto_reset,
                    int random_pose, unsigned long long seed, unsigned long long env_global, const double* policy_params, int ngroups, double* rows_out) {
     using V = Quad<T>;
-    LaneModel<V> m;
-    T tab[LM_TABLE];
-    { int rc = build_packed_model<T>(P, tab); if (rc) return rc; }
-    m.c.inv = tab; m.c.tab = tab + LM_INV; m.c.lean = false; m.c.preload();
-    LaneState<V> s0;
-    s0.px = V(T(qpos[0])); s0.py = V(T(qpos[1])); s0.pz = V(T(qpos[2]));
-    s0.qw = V(T(qpos[3])); s0.qx = V(T(qpos[4])); s0.qy = V(T(qpos[5])); s0.qz = V(T(qpos[6]));
-    auto lo = [](double x) { return V(T(x - (double)T(x))); };
-    s0.pz_lo = lo(qpos[2]); s0.qw_lo = lo(qpos[3]); s0.qx_lo = lo(qpos[4]); s0.qy_lo = lo(qpos[5]); s0.qz_lo = lo(qpos[6]);
-    s0.vx = V(T(qvel[0])); s0.vy = V(T(qvel[1])); s0.vz = V(T(qvel[2]));
-    s0.wx = V(T(qvel[3])); s0.wy = V(T(qvel[4])); s0.wz = V(T(qvel[5]));
-    double ph = qpos[15], kk = std::floor((ph + M_PI) / (2 * M_PI));
-    s0.phi = V(T(ph - kk * 2 * M_PI)); s0.turns = V(T(kk)); s0.phid = V(T(qvel[14]));
-    s0.th1 = V(T(qpos[7]), T(qpos[9]), T(qpos[11]), T(qpos[13]));
-    s0.th2 = V(T(qpos[8]), T(qpos[10]), T(qpos[12]), T(qpos[14]));
-    s0.thd1 = V(T(qvel[6]), T(qvel[8]), T(qvel[10]), T(qvel[12]));
-    s0.thd2 = V(T(qvel[7]), T(qvel[9]), T(qvel[11]), T(qvel[13]));
-    for (int i = 0; i < 3; i++) { s0.wa[i] = V(T(0)); s0.wl[i] = V(T(0)); }
-    s0.wj[0] = s0.wj[1] = V(T(0)); s0.wm = V(T(0)); s0.fail = V(T(0));
-    SimOpts o; o.contacts = 1; o.max_newton = 12; o.implicit_damp = 1; o.rank_one = 1; o.lean = 0; o.offload = (g_offload && ngroups >= 2) ? 1 : 0; o.prof = nullptr; o.hist = nullptr;
-    o.spread = g_spread;
-    o.aux = (g_aux && o.offload && ngroups == 4) ? 1 : 0;
-    T auxtab[LM_AUX];
-    build_aux_block<T>(tab, auxtab);
-    LaneModel<V> m_aux = m;
-    m_aux.c.tab = auxtab; m_aux.c.tab_rare = tab + LM_INV; m_aux.c.preload();
-    V scratch[SC_COUNT];
+    HostRun<T> w;
+    if (int rc = w.init(P, ngroups, false, false, 1, 12, 1, 1)) return rc;
     const int D = obs_dim(task);
     TaskOpts topt; topt.task = task; topt.step_limit = step_limit; topt.auto_reset = auto_reset; topt.random_pose = random_pose; topt.seed = seed; topt.env_global = env_global;
     PolicyParams<T> pp = default_policy_params<T>();
     if (policy_params) { pp.kick_angle = T(policy_params[0]); pp.speed = T(policy_params[1]); pp.angle_threshold = T(policy_params[2]); }
     LaneState<V> s_final;
     EpisodeRegs<T> er_final;
-    HostWave wave;
-    wave.ngrp = ngroups; wave.gstride = 16;
-    auto body = [&](int g) {
-        if (ngroups > 1) { g_host_wave = &wave; g_host_grp = g; }
-        LaneScratch<V> sc; sc.p = scratch; sc.stride = 1; sc.grp = g; sc.ngrp = ngroups; sc.gstride = ngroups > 1 ? 16 : 4;
-        sc.ovc = scratch + SC_OVC; sc.ovc_stride = 1; sc.red_lds = true; sc.pd = SC_PD; sc.pd2 = SC_PD2 - SC_OVC;
-        sc.aux_lane = o.aux && g >= 2;
-        const LaneModel<V>& mg = sc.aux_lane ? m_aux : m;
-        const bool rep = g == 0 || (o.offload && g == 1) || sc.aux_lane;          // the lanes that hold the env's state (main, replica, aux)
-        LaneState<V> s = s0;
-        if (!rep) {
-            s.px = s.py = s.pz = V(T(0)); s.qw = V(T(1)); s.qx = s.qy = s.qz = V(T(0)); s.vx = s.vy = s.vz = s.wx = s.wy = s.wz = V(T(0));
-            s.pz_lo = s.qw_lo = s.qx_lo = s.qy_lo = s.qz_lo = V(T(0));
-            s.phi = s.phid = s.turns = V(T(0)); s.th1 = s.th2 = s.thd1 = s.thd2 = V(T(0));
-        }
+    w.run(state_from_qpos<T>(qpos, qvel), [&](typename HostRun<T>::Group& G) {
+        const LaneModel<V>& mg = *G.m;
+        LaneState<V>& s = G.s;
+        const bool rep = G.rep;
         EpisodeRegs<T> er;
         er.step_count = counters[0]; er.episode = (uint32_t)counters[1];
         er.tgt[0] = T(target[0]); er.tgt[1] = T(target[1]); er.tgt[2] = T(target[2]);
-        if (g == 0) {
-            for (int k = 0; k < SC_COUNT; k++) scratch[k] = V(std::numeric_limits<T>::quiet_NaN());
-            if (o.offload) for (int k = 0; k < 56; k++) scratch[SC_ZERO + k] = V(T(0));
-        }
         T ctrl_next = T(0);
         if (!actions && rep) {
             T obs0[19];
@@ -225,40 +207,23 @@ static int rollout(const double* P, double* qpos, double* qvel, double* target, 
             if (actions && rep) ctrl = T(actions[k]);
             if (rep) normalise_state(s);
             for (int i = 0; i < nsub; i++) {
-                if (ngroups > 1) wave.barrier();
-                if (g == 0) for (int q = 0; q < (o.offload ? SC_ZERO : SC_COUNT); q++) scratch[q] = V(std::numeric_limits<T>::quiet_NaN());
-                if (ngroups > 1) wave.barrier();
-                substep<V>(mg, sc, s, V(ctrl), o);
+                w.before_substep(G, false, i == 0);      // (no pair contact here: every slot is poisoned before every substep)
+                substep<V>(mg, G.sc, s, V(ctrl), w.o);
             }
             if (!rep) continue;
             T obs[19], rew;
             bool done;
             control_step_tail<V>(topt, mg, s, er, obs, rew, done);
             if (!actions) ctrl_next = heuristic_policy<T>(task, obs, 1, pp);
-            if (g == 0) {
+            if (G.g == 0) {
                 double* row = rows_out + (size_t)k * (D + 2);
                 for (int j = 0; j < D; j++) row[j] = (double)obs[j];
                 row[D] = (double)rew; row[D + 1] = done ? 1.0 : 0.0;
             }
         }
-        if (g == 0) { s_final = s; er_final = er; }
-        g_host_wave = nullptr;
-    };
-    if (ngroups <= 1) body(0);
-    else {
-        std::vector<std::thread> th;
-        for (int g = 1; g < ngroups; g++) th.emplace_back(body, g);
-        body(0);
-        for (auto& t : th) t.join();
-    }
-    const LaneState<V>& s = s_final;
-    T nq = std::sqrt(s.qw.v[0] * s.qw.v[0] + s.qx.v[0] * s.qx.v[0] + s.qy.v[0] * s.qy.v[0] + s.qz.v[0] * s.qz.v[0]);
-    qpos[0] = s.px.v[0]; qpos[1] = s.py.v[0]; qpos[2] = (double)s.pz.v[0] + (double)s.pz_lo.v[0];
-    qpos[3] = ((double)s.qw.v[0] + (double)s.qw_lo.v[0]) / nq; qpos[4] = ((double)s.qx.v[0] + (double)s.qx_lo.v[0]) / nq;
-    qpos[5] = ((double)s.qy.v[0] + (double)s.qy_lo.v[0]) / nq; qpos[6] = ((double)s.qz.v[0] + (double)s.qz_lo.v[0]) / nq;
-    qvel[0] = s.vx.v[0]; qvel[1] = s.vy.v[0]; qvel[2] = s.vz.v[0]; qvel[3] = s.wx.v[0]; qvel[4] = s.wy.v[0]; qvel[5] = s.wz.v[0];
-    for (int l = 0; l < 4; l++) { qpos[7 + 2 * l] = s.th1.v[l]; qpos[8 + 2 * l] = s.th2.v[l]; qvel[6 + 2 * l] = s.thd1.v[l]; qvel[7 + 2 * l] = s.thd2.v[l]; }
-    qpos[15] = (double)s.phi.v[0] + 2 * M_PI * (double)s.turns.v[0]; qvel[14] = s.phid.v[0];
+        if (G.g == 0) { s_final = s; er_final = er; }
+    });
+    qpos_from_state<T>(s_final, qpos, qvel);
     target[0] = er_final.tgt[0]; target[1] = er_final.tgt[1]; target[2] = er_final.tgt[2];
     counters[0] = er_final.step_count; counters[1] = (int)er_final.episode;
     return 0;
@@ -274,10 +239,8 @@ extern "C" int jbh_rollout(const double* P, double* qpos, double* qvel, double* 
 extern "C" int jbh_substep_record(const double* P, const float* rec, int max_newton, int ngroups, int trace, double* fail_out) {
     using T = float;
     using V = Quad<T>;
-    LaneModel<V> m;
-    T tab[LM_TABLE];
-    { int rc = build_packed_model<T>(P, tab); if (rc) return rc; }
-    m.c.inv = tab; m.c.tab = tab + LM_INV; m.c.lean = false; m.c.preload();
+    HostRun<T> w;
+    if (int rc = w.init(P, ngroups, false, false, 1, max_newton, 1, 1)) return rc;
     LaneState<V> s0;
     const T ctrl = rec[0];
     s0.px = V(rec[1]); s0.py = V(rec[2]); s0.pz = V(rec[3]); s0.qw = V(rec[4]); s0.qx = V(rec[5]); s0.qy = V(rec[6]); s0.qz = V(rec[7]);
@@ -290,49 +253,44 @@ extern "C" int jbh_substep_record(const double* P, const float* rec, int max_new
     s0.th1 = V(l[0], l[6], l[12], l[18]); s0.th2 = V(l[1], l[7], l[13], l[19]); s0.thd1 = V(l[2], l[8], l[14], l[20]); s0.thd2 = V(l[3], l[9], l[15], l[21]);
     s0.wj[0] = V(l[4], l[10], l[16], l[22]); s0.wj[1] = V(l[5], l[11], l[17], l[23]);
     s0.fail = V(T(0));
-    SimOpts o; o.contacts = 1; o.max_newton = max_newton; o.implicit_damp = 1; o.rank_one = 1; o.lean = 0; o.offload = (g_offload && ngroups >= 2) ? 1 : 0; o.prof = nullptr; o.hist = nullptr;
-    o.spread = g_spread;
-    o.aux = (g_aux && o.offload && ngroups == 4) ? 1 : 0;
-    T auxtab[LM_AUX];
-    build_aux_block<T>(tab, auxtab);
-    LaneModel<V> m_aux = m;
-    m_aux.c.tab = auxtab; m_aux.c.tab_rare = tab + LM_INV; m_aux.c.preload();
-    V scratch[SC_COUNT];
-    HostWave wave;
-    wave.ngrp = ngroups; wave.gstride = 16;
     LaneState<V> s_final;
     g_ls_trace = trace;
-    auto body = [&](int g) {
-        if (ngroups > 1) { g_host_wave = &wave; g_host_grp = g; }
-        LaneScratch<V> sc; sc.p = scratch; sc.stride = 1; sc.grp = g; sc.ngrp = ngroups; sc.gstride = ngroups > 1 ? 16 : 4;
-        sc.ovc = scratch + SC_OVC; sc.ovc_stride = 1; sc.red_lds = true; sc.pd = SC_PD; sc.pd2 = SC_PD2 - SC_OVC;
-        sc.aux_lane = o.aux && g >= 2;
-        const bool rep = g == 0 || (o.offload && g == 1) || sc.aux_lane;
-        LaneState<V> s = s0;
-        if (!rep) {
-            s.px = s.py = s.pz = V(T(0)); s.qw = V(T(1)); s.qx = s.qy = s.qz = V(T(0)); s.vx = s.vy = s.vz = s.wx = s.wy = s.wz = V(T(0));
-            s.pz_lo = s.qw_lo = s.qx_lo = s.qy_lo = s.qz_lo = V(T(0));
-            s.phi = s.phid = s.turns = V(T(0)); s.th1 = s.th2 = s.thd1 = s.thd2 = V(T(0));
-        }
-        if (g == 0) {
-            for (int k = 0; k < SC_COUNT; k++) scratch[k] = V(std::numeric_limits<T>::quiet_NaN());
-            if (o.offload) for (int k = 0; k < 56; k++) scratch[SC_ZERO + k] = V(T(0));
-        }
-        if (ngroups > 1) wave.barrier();
-        substep<V>(sc.aux_lane ? m_aux : m, sc, s, V(ctrl), o);
-        if (g == 0) s_final = s;
-        g_host_wave = nullptr;
-    };
-    if (ngroups <= 1) body(0);
-    else {
-        std::vector<std::thread> th;
-        for (int g = 1; g < ngroups; g++) th.emplace_back(body, g);
-        body(0);
-        for (auto& t : th) t.join();
-    }
+    w.run(s0, [&](typename HostRun<T>::Group& G) {
+        w.sync();
+        substep<V>(*G.m, G.sc, G.s, V(ctrl), w.o);
+        if (G.g == 0) s_final = G.s;
+    });
     g_ls_trace = 0;
     if (fail_out) *fail_out = s_final.fail.v[0];
     return 0;
+}
+// jb_variant.hpp for the tests.  out = [JB_VARIANT_* id or -1 (no kernel), bytes of dynamic LDS, main lanes, lane groups, offload, aux, split tables,
+// scratch floats per lane, pd, pd2, red_lds, waves per SIMD, floats per lane of the block in global memory]; then, from jb_sim.hpp, what the
+// layout is stated in: [SC_PD, SC_PD_LEAN, SC_PD2 - SC_OVC, 4 * (NSLOT - ROW_K), SC_COUNT, SC_COUNT_LEAN, SC_COUNT_LEAN_PAIR].  Returns out[0].
+extern "C" int jbh_step_layout(int lean, int pair, int per_env_model, int epw, int* out) {
+    const StepLayout l = step_layout(epw, lean != 0, pair != 0);
+    const int v[20] = {step_variant(lean != 0, pair != 0, per_env_model != 0, epw), (int)step_lds_bytes(l, per_env_model != 0), l.main_lanes, l.groups, l.offload, l.aux, l.split_tables,
+                       l.scratch_floats, l.pd, l.pd2, l.red_lds, l.waves_per_simd, l.ovc_floats,
+                       SC_PD, SC_PD_LEAN, SC_PD2 - SC_OVC, 4 * (NSLOT - ROW_K), SC_COUNT, SC_COUNT_LEAN, SC_COUNT_LEAN_PAIR};
+    for (int i = 0; i < 20; i++) out[i] = v[i];
+    return v[0];
+}
+// What jb_variant.hpp's helpers hand a lane of group grp in the (lean, pair, epw) wave, with the device's stride (the main lanes).  out = [stride,
+// grp, ngrp, gstride, floats from the lane's scratch base to its overflow candidates or -1 (outside the scratch), ovc_stride, pd, pd2, red_lds,
+// aux_lane, holds_state, SimOpts lean / offload / aux, SC_OVC]
+extern "C" void jbh_lane_binding(int lean, int pair, int epw, int grp, int* out) {
+    const StepLayout l = step_layout(epw, lean != 0, pair != 0);
+    static Quad<float> lds[1], ext[1];       // (addresses only)
+    LaneScratch<Quad<float>> sc;
+    bind_scratch(sc, l, lds, l.main_lanes, grp, ext);
+    const SimOpts o = sim_opts(l, 1, 12, 1, 1, 1);
+    const int v[15] = {sc.stride, sc.grp, sc.ngrp, sc.gstride, sc.ovc == ext ? -1 : (int)(sc.ovc - lds), sc.ovc_stride, sc.pd, sc.pd2, sc.red_lds, sc.aux_lane, holds_state(l, grp),
+                       o.lean, o.offload, o.aux, SC_OVC};
+    for (int i = 0; i < 15; i++) out[i] = v[i];
+}
+extern "C" void jbh_wave_order_plan(int grid, int wave_slots, int waves_per_simd, int* out) {
+    const WaveOrderPlan p = wave_order_plan(grid, wave_slots, waves_per_simd);
+    out[0] = p.reorder; out[1] = p.fold_from;
 }
 // the line-searched second solve (jb_sim.hpp newton_phase<LS = true>): [substeps solved a second time, outer passes of those solves, passes whose
 // line search shortened the step, second solves that ended at NEWTON_LS_CAP]

@@ -527,6 +527,31 @@ def test_all_geoms_contact_parity(variant):
     g.close()
 
 
+LAUNCH_ROWS = [(v, epw) for v, epws in (("ordinary", (1, 2, 4, 8)), ("pair", (1, 2, 4, 8)), ("lean", (1, 2, 4)), ("lean_pair", (4,))) for epw in epws]
+
+
+@pytest.mark.parametrize("variant,epw", LAUNCH_ROWS, ids=["%s-%d" % r for r in LAUNCH_ROWS])
+def test_every_launch_row_against_the_oracle(variant, epw):
+    """Every row of the launch table (jb_variant.hpp STEP_ROWS: the 12 step-kernel instantiations) under the strict protocol, teacher-forced:
+    two full waves and a ragged one, 8 control steps of uniform actions.  The handle must report the row it was asked for.
+    The zero caps are conditions, not measurements: on these inputs the oracle alone has no near-switch and no deep env-step (checked on the
+    CPU with OracleEnv.conditioning() for n = 3, 5, 9, 17 nominal and n = 9 augmented at seed 3: the smallest switch margin is 1.1e-7 m against
+    MARGIN_TOL 1.1e-8), so every env-step is in the well class and is held to the suite's well-class line, 2e-5."""
+    from jitterbug_amd import _lib, augmented_jitterbug as aj
+    from jitterbug_amd.vec_env import JitterbugVecEnv
+    n = 2 * epw + 1
+    flags = {"ordinary": 0, "pair": _lib.FLAG_PAIR, "lean": _lib.FLAG_LEAN, "lean_pair": _lib.FLAG_LEAN}[variant]
+    params = aj.augmented_params(n, seed=3) if variant == "lean_pair" else None
+    g = JitterbugVecEnv(n, "move_to_pose", seed=3, params=params, flags=flags, envs_per_wave=epw)
+    assert g.kernel_variant == variant and g.envs_per_wave == epw
+    g.close()
+    r = _teacher_forced("move_to_pose", n, 8, seed=3, params=params, flags=flags, envs_per_wave=epw)
+    print("launch row %s at %d envs per wave:" % (variant, epw), r)
+    assert r["kernel_variant"] == variant, r
+    assert_protocol(r, well_bad=0, worst_well=2e-5, near_cap=0)
+    assert r["deep_steps"] == 0, protocol_message(r)
+
+
 def test_auto_reset_and_episode_streams():
     g, o = _envs(50, "move_to_position", seed=9, time_limit=0.05)      # 5 control steps per episode
     o2 = None

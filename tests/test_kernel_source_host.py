@@ -638,3 +638,136 @@ def test_line_searched_solve_settles_rounding_level_cycles_fp32(params):
             assert fail[0] == 0
     st = _ls_stats()
     assert st[0] >= 4 and st[3] == 0, st          # the cycling records did go through the second solve, and it settled every one
+
+
+# ---------------------------------------------------------------------------------------------- the step-kernel variants (jb_variant.hpp)
+VARIANT_ORDINARY, VARIANT_PAIR, VARIANT_LEAN, VARIANT_LEAN_PAIR = 0, 1, 2, 3          # include/jitterbug_hip.h JB_VARIANT_*
+# (variant, envs per wave, one model per env) -> bytes of dynamic LDS of the launch.  Provenance: launch_step's own expression in jb_api.hip as
+# it stood BEFORE jb_variant.hpp existed (commit 20a9ece, lines 1166-1169), evaluated once in a stand-alone host program against that commit's
+# jb_sim.hpp for every combination that commit launches.  Literals on purpose: never recomputed from the code under test.
+PARENT_LDS_BYTES = {
+    (0, 1, 0): 10132, (0, 1, 1): 10132, (0, 2, 0): 16116, (0, 2, 1): 20264, (0, 4, 0): 28084, (0, 4, 1): 40528, (0, 8, 0): 50996, (0, 8, 1): 72864,
+    (1, 1, 0): 9108, (1, 1, 1): 9108, (1, 2, 0): 15092, (1, 2, 1): 18216, (1, 4, 0): 27060, (1, 4, 1): 36432, (1, 8, 0): 50996, (1, 8, 1): 72864,
+    (2, 1, 0): 7140, (2, 1, 1): 7140, (2, 2, 0): 11572, (2, 2, 1): 14280, (2, 4, 0): 20436, (2, 4, 1): 28560,
+    (3, 4, 1): 19968,
+}
+LAYOUT_KEYS = ("variant", "lds_bytes", "main_lanes", "groups", "offload", "aux", "split_tables", "scratch_floats", "pd", "pd2", "red_lds", "waves_per_simd", "ovc_floats",
+               "SC_PD", "SC_PD_LEAN", "SC_PD2_minus_SC_OVC", "overflow_floats", "SC_COUNT", "SC_COUNT_LEAN", "SC_COUNT_LEAN_PAIR")
+
+
+@pytest.fixture(scope="module")
+def step_layout():
+    import tests.build_harness as bh
+    lib = C.CDLL(bh.build())
+    lib.jbh_step_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+
+    def layout(lean, pair, per_env, epw):
+        out = (C.c_int * len(LAYOUT_KEYS))()
+        rc = lib.jbh_step_layout(int(lean), int(pair), int(per_env), epw, out)
+        d = dict(zip(LAYOUT_KEYS, out))
+        assert rc == d["variant"]
+        return d
+    return layout
+
+
+def _parent_variant(lean, pair, per_env, epw):
+    """What the launcher ran before the table: kernel_variant() behind check_variant() and create_impl's clamp of LEAN to 4 envs per wave."""
+    if lean and pair:
+        return VARIANT_LEAN_PAIR if per_env and epw == 4 else None
+    if lean:
+        return VARIANT_LEAN if epw <= 4 else None
+    return VARIANT_PAIR if pair else VARIANT_ORDINARY
+
+
+def test_launchable_set_is_the_twelve_kernels_with_their_variant_ids(step_layout):
+    rows = set()
+    for lean in (0, 1):
+        for pair in (0, 1):
+            for per_env in (0, 1):
+                for epw in (1, 2, 4, 8):
+                    want = _parent_variant(lean, pair, per_env, epw)
+                    got = step_layout(lean, pair, per_env, epw)["variant"]
+                    assert got == (-1 if want is None else want), (lean, pair, per_env, epw, got)
+                    if want is not None:
+                        rows.add((want, epw))
+    assert rows == ({(VARIANT_ORDINARY, e) for e in (1, 2, 4, 8)} | {(VARIANT_PAIR, e) for e in (1, 2, 4, 8)} | {(VARIANT_LEAN, e) for e in (1, 2, 4)} | {(VARIANT_LEAN_PAIR, 4)})
+    assert len(rows) == 12
+    # LEAN with the pair contact only for one model per env at four envs per wave; no LEAN kernel at eight
+    assert [step_layout(1, 1, pe, e)["variant"] for pe in (0, 1) for e in (1, 2, 4, 8)] == [-1, -1, -1, -1, -1, -1, VARIANT_LEAN_PAIR, -1]
+    assert step_layout(1, 0, 0, 8)["variant"] == -1 and step_layout(1, 0, 1, 8)["variant"] == -1
+    # every launchable combination is one the table of expected LDS sizes covers, and the other way round
+    launchable = {(step_layout(l, p, pe, e)["variant"], e, pe) for l in (0, 1) for p in (0, 1) for pe in (0, 1) for e in (1, 2, 4, 8)}
+    assert {k for k in launchable if k[0] >= 0} == set(PARENT_LDS_BYTES)
+
+
+def test_lds_bytes_of_every_launchable_row_equal_the_previous_launcher_s(step_layout):
+    flags = {VARIANT_ORDINARY: (0, 0), VARIANT_PAIR: (0, 1), VARIANT_LEAN: (1, 0), VARIANT_LEAN_PAIR: (1, 1)}
+    for (variant, epw, per_env), want in PARENT_LDS_BYTES.items():
+        lean, pair = flags[variant]
+        d = step_layout(lean, pair, per_env, epw)
+        assert d["variant"] == variant and d["lds_bytes"] == want, (variant, epw, per_env, d["lds_bytes"], want)
+
+
+def test_layout_facts_are_the_step_kernel_s(step_layout):
+    for lean in (0, 1):
+        for pair in (0, 1):
+            for epw in (1, 2, 4, 8):
+                d = step_layout(lean, pair, 1, epw)
+                assert d["main_lanes"] == 4 * epw and d["groups"] == (2 if epw == 8 else 4)
+                assert d["offload"] == (not lean)
+                assert d["aux"] == (not lean and not pair and d["groups"] == 4)
+                assert d["split_tables"] == (lean and pair)
+                assert d["pd"] == (d["SC_PD_LEAN"] if lean else d["SC_PD"])
+                assert d["pd2"] == (d["overflow_floats"] if lean else d["SC_PD2_minus_SC_OVC"])
+                assert d["red_lds"] == (not lean)
+                assert d["scratch_floats"] == ((d["SC_COUNT_LEAN_PAIR"] if pair else d["SC_COUNT_LEAN"]) if lean else d["SC_COUNT"])
+                assert d["waves_per_simd"] == (2 if lean else 1)
+                assert d["ovc_floats"] == (d["overflow_floats"] + 9 if lean else 0)
+    assert d["overflow_floats"] == 4 * (30 - 9)          # 4 * (NSLOT - ROW_K) of the default build
+
+
+def test_wave_order_plan():
+    """Launch order: more waves than the device holds at once are launched longest first; with two waves per SIMD and the whole batch
+    resident only the waves beyond one per SIMD are folded onto the ones before."""
+    import tests.build_harness as bh
+    lib = C.CDLL(bh.build())
+    lib.jbh_wave_order_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+
+    def plan(grid, per_simd):
+        out = (C.c_int * 2)(-7, -7)
+        lib.jbh_wave_order_plan(grid, 1024, per_simd, out)
+        return bool(out[0]), out[1]
+
+    for grid in (1, 1024):
+        assert plan(grid, 1)[0] is False and plan(grid, 2)[0] is False
+    for grid in (1025, 2048, 2049, 4096):
+        assert plan(grid, 1) == (True, 0)
+    for grid in (1025, 2048):
+        assert plan(grid, 2) == (True, 1024)
+    for grid in (2049, 4096):
+        assert plan(grid, 2) == (True, 0)
+
+
+def test_host_lane_binding_is_what_the_step_kernel_states(step_layout):
+    """jb_variant.hpp's bind_scratch / holds_state / sim_opts - what the host harness hands a lane - against the statements of jb_api.hip's
+    step_body, written out here: the kernel keeps its own copy inline, and this is what ties the two."""
+    import tests.build_harness as bh
+    lib = C.CDLL(bh.build())
+    lib.jbh_lane_binding.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)]
+    keys = ("stride", "grp", "ngrp", "gstride", "ovc_offset", "ovc_stride", "pd", "pd2", "red_lds", "aux_lane", "holds_state", "o_lean", "o_offload", "o_aux", "SC_OVC")
+    for lean in (0, 1):
+        for pair in (0, 1):
+            for epw in (1, 2, 4, 8):
+                f = step_layout(lean, pair, 1, epw)
+                MAIN, NGRP = 4 * epw, 2 if epw == 8 else 4
+                AUX, OFFLOAD = (not lean and not pair and NGRP == 4), not lean
+                for grp in range(NGRP):
+                    out = (C.c_int * len(keys))()
+                    lib.jbh_lane_binding(lean, pair, epw, grp, out)
+                    b = dict(zip(keys, out))
+                    assert (b["stride"], b["grp"], b["ngrp"], b["gstride"], b["ovc_stride"]) == (MAIN, grp, NGRP, MAIN, MAIN), b
+                    assert b["ovc_offset"] == (-1 if lean else b["SC_OVC"] * MAIN), b          # LEAN: the block in global memory
+                    assert b["pd"] == (f["SC_PD_LEAN"] if lean else f["SC_PD"]) and b["pd2"] == (f["overflow_floats"] if lean else f["SC_PD2_minus_SC_OVC"]), b
+                    assert b["red_lds"] == (not lean) and b["aux_lane"] == (AUX and grp >= 2), b
+                    assert b["holds_state"] == (grp == 0 or (OFFLOAD and grp == 1) or b["aux_lane"]), b
+                    assert (b["o_lean"], b["o_offload"], b["o_aux"]) == (lean, OFFLOAD, AUX), b
