@@ -221,6 +221,41 @@ int jb_step_many(jb_handle* h, int32_t n_steps, const float* actions, float* row
 /* frees the device staging jb_step_many / jb_rollout_policy have grown (K x N x (D+2) floats: 4-5 GB after one rollout(1000) of 65 536 envs);
  * the next call of either allocates what it needs again */
 int jb_release_staging(jb_handle* h);
+/* Exact snapshot, restore and fork of the simulator state (additive in ABI 5).  Everything a handle carries from one launch to the next
+ * is 232 bytes per env: the root block (pose, velocities, the contact solver's warm start, the failure / cap counter, the target), the leg
+ * block, the step counters and the episode counters (the RNG is stateless: keyed by seed, global env, episode, stream).  A snapshot is
+ * those raw blocks, field major: root [32][n] | leg [6][4n] | step_count [n] | episode [n].  A handle restored from a snapshot continues
+ * BIT FOR BIT as the handle the snapshot was taken from would have: same rows, same time-limit done flags, same reset poses - which
+ * jb_get_state / jb_set_state do not give (fp64 MuJoCo layout, warm start cleared, step and episode counters untouched).
+ *   jb_snapshot_device  the state -> d_snap (jb_snapshot_bytes = 232 * N bytes of device memory), one launch, asynchronous
+ *   jb_restore_device   d_snap, a snapshot of n_src envs -> the state.  d_src [N] (device, nullable): env j of the handle receives env
+ *                       d_src[j] of the snapshot - a FORK: one plant state fanned out into many model lanes, n_src need not be N.  Without
+ *                       a map n_src must be N.  One launch, asynchronous; the kernel clamps every index into [0, n_src), so a bad
+ *                       device-side map selects a wrong env, never memory outside the snapshot.
+ *   jb_snapshot / jb_restore  host forms (synchronous): blob = a 64-byte header (magic, layout version, n_envs, task_id, substeps,
+ *                       step_limit, field counts) + the raw blocks, jb_snapshot_host_bytes in all.  jb_restore returns JB_E_INVALID, before
+ *                       anything is launched, for a wrong magic / version / field count, a blob_bytes that does not match the header, a
+ *                       task_id other than the handle's (the target's meaning differs by task) and a src [N] (host, nullable) entry
+ *                       outside [0, n_src); without src the blob's n_envs must be N.
+ * Every form refuses a handle with a jb_step_async pending.
+ * A snapshot does NOT contain the model tables: restoring onto a handle with other tables (per-env randomised ones included) is allowed
+ * and is the caller's statement that the models match.  Bit-exact continuation across handles also needs the same kernel variant (see
+ * JB_FLAG_LEAN: the variants agree to fp32 rounding only) and the same envs_per_wave, the same seed and env_offset (they key the draws of
+ * later resets - a fork deliberately gives the lanes of one group different keys), and the same task options.
+ *   jb_score_tapes_device  K fused steps from the CURRENT state in one launch of the step kernel - d_tapes [K, N] action tapes (env n
+ *                       applies column n), NULL = the in-kernel heuristic policy - then per env the discounted return
+ *                       sum_k gamma^k r_k up to and including the first step whose done flag is set (what follows an in-kernel reset is
+ *                       another episode) into d_returns [N], and the number of steps counted into d_alive [N] (nullable; K when the env
+ *                       was never done).  fp32, in the order acc = fmaf(g, r_k, acc); g *= gamma.  Rewards and done flags of the steps go
+ *                       to staging owned by the handle (grow-only; jb_release_staging frees it).  The handle is left in the post-rollout
+ *                       state: restore to go back.  Asynchronous on the handle's stream. */
+int64_t jb_snapshot_bytes(jb_handle* h);
+int jb_snapshot_device(jb_handle* h, void* d_snap);
+int jb_restore_device(jb_handle* h, const void* d_snap, int32_t n_src, const int32_t* d_src /*[N] nullable*/);
+int64_t jb_snapshot_host_bytes(jb_handle* h);
+int jb_snapshot(jb_handle* h, void* blob);
+int jb_restore(jb_handle* h, const void* blob, int64_t blob_bytes, const int32_t* src /*[N] nullable, host*/);
+int jb_score_tapes_device(jb_handle* h, int32_t n_steps, const float* d_tapes /*[K,N] nullable*/, float gamma, float* d_returns /*[N]*/, int32_t* d_alive /*[N] nullable*/);
 /* seconds each wave of the LAST step launch was alive (one wave = jb_envs_per_wave envs), out[0 .. min(n_waves, max_waves)); returns the
  * number of waves.  Mean against maximum is the load imbalance of the launch (roofline). */
 int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves);

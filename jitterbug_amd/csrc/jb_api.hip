@@ -28,6 +28,7 @@
 #include "jb_nominal_spec.h"
 #include "jb_owned.hpp"
 #include "jb_sim.hpp"
+#include "jb_snapshot.hpp"
 #include "jb_step.hpp"
 #include "jb_task.hpp"
 #include "jb_variant.hpp"
@@ -43,6 +44,7 @@ namespace {
 
 enum RootF : int { RF_P = 0, RF_Q = 3, RF_V = 7, RF_W = 10, RF_PHI = 13, RF_PHID = 14, RF_TURNS = 15, RF_WA = 16, RF_WL = 19, RF_WM = 22, RF_FAIL = 23, RF_TGT = 24, RF_LO = 27 /*5: low-order words of z and the quaternion*/, ROOT_F = 32 };
 enum LegF : int { LF_TH1 = 0, LF_TH2 = 1, LF_THD1 = 2, LF_THD2 = 3, LF_WJ0 = 4, LF_WJ1 = 5, LEG_F = 6 };
+static_assert(ROOT_F == SNAP_ROOT_F && LEG_F == SNAP_LEG_F, "jb_snapshot.hpp copies exactly the state blocks declared here");
 
 struct KArgs {
     int n, task, substeps, step_limit, auto_reset, contacts, max_newton, random_pose, per_env_model;
@@ -745,6 +747,8 @@ struct jb_handle {
     Dev<unsigned long long> d_wave_stats, d_wave_clock, d_resolve;      // -DJB_WAVE_STATS builds; the last launch's wave lifetimes; [1]: KArgs::resolve_count
     Dev<float> d_capture; Dev<unsigned> d_capture_count;      // diagnostic builds (-DJB_CAPTURE)
     Dev<float> d_tape, d_rows_stage, d_rew_stage;      // staging of the host-buffer rollouts (jb_step_many, jb_rollout_policy): grow-only
+    Dev<unsigned char> d_done_stage;                   // jb_score_tapes_device: the done flags of every step, next to d_rew_stage (grow-only)
+    Dev<uint32_t> d_snap_stage; Dev<int> d_src_stage;  // jb_snapshot / jb_restore: the raw blocks and the index map on their way to / from the host (grow-only)
     Dev<int> d_wave_order;           // launch order of the waves (jb_wave_order_kernel), empty while the device holds the whole batch at once
     int wave_slots;                  // waves the device holds at once with this handle's kernel variant
     EncArgs enc;          // observation encoder (n_layers = 0: none)
@@ -908,6 +912,13 @@ static int upload_model(jb_handle* h, const double* params, int n_tables) {
     JB_HIP(hipMemcpyAsync(fresh ? fresh.get() : h->d_model.get(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     install_model(h, std::move(fresh), per_env_model, pair);
+    return JB_OK;
+}
+// grow-only device staging of any element type (ensure_stage below is the float form the rollouts use)
+template <typename T> static int grow_stage(jb_handle* h, Dev<T>& buf, size_t n, const char* what) {
+    if (n <= buf.size()) return JB_OK;
+    if (buf) JB_HIP(hipStreamSynchronize(h->stream));      // (the buffer may still be in use by queued work)
+    if (buf.alloc(n) != hipSuccess) return fail(JB_E_HIP, std::string("out of device memory for ") + what);
     return JB_OK;
 }
 
@@ -1267,7 +1278,112 @@ int jb_step_many(jb_handle* h, int32_t n_steps, const float* actions, float* row
 int jb_release_staging(jb_handle* h) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
-    h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset();
+    h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset(); h->d_done_stage.reset();
+    h->d_snap_stage.reset(); h->d_src_stage.reset();
+    return JB_OK;
+}
+// ---------------------------------------------------------------------------------------------- snapshot / restore / fork, tape scoring
+// (jb_snapshot.hpp: a snapshot is the four state blocks back to back; every form below is ONE launch of jb_fork_kernel)
+static SnapView state_view(jb_handle* h) {
+    SnapView v;
+    v.root = (uint32_t*)h->d_root.get(); v.leg = (uint32_t*)h->d_leg.get(); v.step = (uint32_t*)h->d_step.get(); v.episode = (uint32_t*)h->d_episode.get();
+    v.n = h->cfg.n_envs;
+    return v;
+}
+static int launch_fork(jb_handle* h, const SnapView& dst, const SnapView& src, const int* d_map) {
+    const long long total = (long long)SNAP_WORDS * dst.n;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;      // (grid-stride beyond 2 M words)
+    hipLaunchKernelGGL(jb_fork_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, dst, src, d_map);
+    JB_HIP(hipGetLastError());
+    return JB_OK;
+}
+int64_t jb_snapshot_bytes(jb_handle* h) {
+    if (!h) return fail(JB_E_INVALID, "handle is NULL");
+    return (int64_t)SNAP_ENV_BYTES * (int64_t)h->cfg.n_envs;
+}
+int64_t jb_snapshot_host_bytes(jb_handle* h) {
+    if (!h) return fail(JB_E_INVALID, "handle is NULL");
+    return (int64_t)snap_blob_bytes(h->cfg.n_envs);
+}
+int jb_snapshot_device(jb_handle* h, void* d_snap) {
+    JB_ENTER(h);
+    if (!d_snap) return fail(JB_E_INVALID, "jb_snapshot_device: the snapshot buffer is NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_snapshot_device: a jb_step_async is pending (jb_step_wait first)");
+    RoctxRange range("jb_snapshot");
+    return launch_fork(h, snap_view(d_snap, h->cfg.n_envs), state_view(h), nullptr);
+}
+int jb_restore_device(jb_handle* h, const void* d_snap, int32_t n_src, const int32_t* d_src) {
+    JB_ENTER(h);
+    if (!d_snap) return fail(JB_E_INVALID, "jb_restore_device: the snapshot buffer is NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_restore_device: a jb_step_async is pending (jb_step_wait first)");
+    if (n_src < 1) return fail(JB_E_INVALID, "jb_restore_device: n_src must be >= 1");
+    if (!d_src && n_src != h->cfg.n_envs)
+        return fail(JB_E_INVALID, "jb_restore_device: a snapshot of " + std::to_string(n_src) + " envs onto a handle of " + std::to_string(h->cfg.n_envs) + " needs an index map");
+    RoctxRange range("jb_restore");
+    return launch_fork(h, state_view(h), snap_view(const_cast<void*>(d_snap), n_src), d_src);      // (const_cast: the source side is only read)
+}
+int jb_snapshot(jb_handle* h, void* blob) {
+    JB_ENTER(h);
+    if (!blob) return fail(JB_E_INVALID, "jb_snapshot: blob is NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_snapshot: a jb_step_async is pending (jb_step_wait first)");
+    const size_t N = (size_t)h->cfg.n_envs;
+    int rc = grow_stage(h, h->d_snap_stage, N * SNAP_WORDS, "the snapshot");
+    if (rc) return rc;
+    rc = jb_snapshot_device(h, h->d_snap_stage.get());
+    if (rc) return rc;
+    const SnapHeader hd = snap_make_header(h->cfg.n_envs, h->cfg.task_id, h->cfg.substeps, h->cfg.step_limit);
+    std::memcpy(blob, &hd, sizeof hd);
+    JB_HIP(hipMemcpyAsync((char*)blob + SNAP_HEADER_BYTES, h->d_snap_stage.get(), N * SNAP_ENV_BYTES, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipStreamSynchronize(h->stream));
+    return JB_OK;
+}
+int jb_restore(jb_handle* h, const void* blob, int64_t blob_bytes, const int32_t* src) {
+    JB_ENTER(h);
+    if (!blob) return fail(JB_E_INVALID, "jb_restore: blob is NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_restore: a jb_step_async is pending (jb_step_wait first)");
+    // everything is checked on the host before anything is copied or launched
+    if (blob_bytes < (int64_t)SNAP_HEADER_BYTES) return fail(JB_E_INVALID, "jb_restore: blob is shorter than its header");
+    SnapHeader hd;
+    std::memcpy(&hd, blob, sizeof hd);
+    if (const char* why = snap_check_header(hd, (long long)blob_bytes, h->cfg.task_id)) return fail(JB_E_INVALID, std::string("jb_restore: ") + why);
+    const int N = h->cfg.n_envs, n_src = hd.n_envs;
+    if (!src && n_src != N) return fail(JB_E_INVALID, "jb_restore: a snapshot of " + std::to_string(n_src) + " envs onto a handle of " + std::to_string(N) + " needs an index map");
+    if (src) {
+        const int bad = snap_first_bad_index(src, N, n_src);
+        if (bad >= 0) return fail(JB_E_INVALID, "jb_restore: src[" + std::to_string(bad) + "] = " + std::to_string(src[bad]) + " is outside [0, " + std::to_string(n_src) + ")");
+    }
+    int rc = grow_stage(h, h->d_snap_stage, (size_t)n_src * SNAP_WORDS, "the snapshot");
+    if (rc) return rc;
+    if (src) { rc = grow_stage(h, h->d_src_stage, (size_t)N, "the index map"); if (rc) return rc; }
+    JB_HIP(hipMemcpyAsync(h->d_snap_stage.get(), (const char*)blob + SNAP_HEADER_BYTES, (size_t)n_src * SNAP_ENV_BYTES, hipMemcpyHostToDevice, h->stream));
+    if (src) JB_HIP(hipMemcpyAsync(h->d_src_stage.get(), src, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+    rc = jb_restore_device(h, h->d_snap_stage.get(), n_src, src ? h->d_src_stage.get() : nullptr);
+    const hipError_t e = hipStreamSynchronize(h->stream);      // (the caller's blob and map are free again on return)
+    if (!rc && e != hipSuccess) rc = fail(JB_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+// K fused steps from the current state (the step kernel, through launch_step: rewards and done flags of EVERY step into the handle's
+// staging), then one thread per env folds them into the discounted return.  The handle is left in the post-rollout state.
+int jb_score_tapes_device(jb_handle* h, int32_t n_steps, const float* d_tapes, float gamma, float* d_returns, int32_t* d_alive) {
+    JB_ENTER(h);
+    if (n_steps < 1) return fail(JB_E_INVALID, "jb_score_tapes_device: n_steps must be >= 1");
+    if (!d_returns) return fail(JB_E_INVALID, "jb_score_tapes_device: the returns buffer is NULL");
+    if (!std::isfinite(gamma)) return fail(JB_E_INVALID, "jb_score_tapes_device: gamma must be finite");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_score_tapes_device: a jb_step_async is pending (jb_step_wait first)");
+    RoctxRange range("jb_score_tapes");
+    const size_t N = (size_t)h->cfg.n_envs, K = (size_t)n_steps;
+    int rc = ensure_stage(h, h->d_rew_stage, K * N, "the rewards");
+    if (!rc) rc = grow_stage(h, h->d_done_stage, K * N, "the done flags");
+    if (rc) return rc;
+    StepIO io = StepIO();
+    io.n_steps = n_steps; io.use_policy = d_tapes ? 0 : 1; io.actions = d_tapes;
+    io.reward_out = h->d_rew_stage.get(); io.done_out = h->d_done_stage.get(); io.every_step = 2 | 4;
+    rc = launch_step(h, io, 0);
+    if (rc) return rc;
+    hipLaunchKernelGGL(jb_return_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, (const float*)h->d_rew_stage.get(), (const unsigned char*)h->d_done_stage.get(),
+                       (int)n_steps, (int)N, gamma, d_returns, (int*)d_alive);
+    JB_HIP(hipGetLastError());
     return JB_OK;
 }
 // how long each wave of the last step launch lived, in seconds (s_memrealtime, 100 MHz): out[0 .. n_waves); returns the number of waves

@@ -408,6 +408,51 @@ class JitterbugVecEnv:
         self.state_version += 1
         return rows[..., :-2].copy(), rows[..., -2].copy(), rows[..., -1] > 0.5
 
+    # ---- exact snapshot / restore / fork of the simulator state, and tape scoring (jb_snapshot_device ... jb_score_tapes_device)
+    @property
+    def snapshot_bytes(self):
+        """Bytes of device memory a snapshot of this env takes (232 per env: root | leg | step_count | episode blocks)."""
+        n = int(self._L.jb_snapshot_bytes(self._h))
+        if n < 0:
+            _lib.check(n)
+        return n
+
+    def snapshot_device(self, ptr):
+        """The whole simulator state -> `snapshot_bytes` of device memory at `ptr` (one launch, asynchronous).  Restoring it continues
+        bit for bit: warm start, step and episode counters included - unlike get_state() / set_state()."""
+        _lib.check(self._L.jb_snapshot_device(self._h, ptr))
+
+    def restore_device(self, ptr, n_src=None, src_ptr=None):
+        """A device snapshot of `n_src` envs (default: this env's count) -> the state.  src_ptr: int32 [N] on the device, env j receives
+        the snapshot's env src[j] (a fork; indices are clamped into range by the kernel).  One launch, asynchronous."""
+        _lib.check(self._L.jb_restore_device(self._h, ptr, self.num_envs if n_src is None else int(n_src), src_ptr))
+        self.state_version += 1
+
+    def save_state(self):
+        """The whole simulator state as a host blob (uint8: 64-byte header + raw blocks) - an exact checkpoint for load_state()."""
+        n = int(self._L.jb_snapshot_host_bytes(self._h))
+        if n < 0:
+            _lib.check(n)
+        blob = np.zeros(n, dtype=np.uint8)
+        _lib.check(self._L.jb_snapshot(self._h, _lib.ptr(blob)))
+        return blob
+
+    def load_state(self, blob, src=None):
+        """Restore a save_state() blob (of this env, or of another env of the same task).  src: int [N], env j receives the blob's env
+        src[j]; without it the blob must hold this env's count.  Refused (JitterbugHipError) before anything runs: a damaged or truncated
+        blob, another task's, an index outside the blob."""
+        b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.asarray(blob, dtype=np.uint8).reshape(-1))
+        s = None if src is None else np.ascontiguousarray(np.asarray(src, dtype=np.int32).reshape(self.num_envs))
+        _lib.check(self._L.jb_restore(self._h, _lib.ptr(b), int(b.size), _lib.ptr(s)))
+        self.state_version += 1
+
+    def score_tapes_device(self, n_steps, tapes_ptr, gamma, returns_ptr, alive_ptr=None):
+        """n_steps fused steps from the CURRENT state (tapes_ptr: float32 [n_steps, N] on the device, None = the in-kernel heuristic
+        policy), then the discounted return of every env up to and including its first done step -> returns_ptr float32 [N], and the
+        steps counted -> alive_ptr int32 [N] (optional).  Asynchronous; the env is left in the post-rollout state."""
+        _lib.check(self._L.jb_score_tapes_device(self._h, int(n_steps), tapes_ptr, float(gamma), returns_ptr, alive_ptr))
+        self.state_version += 1
+
     # ---- rows between GPUs through the library's own RCCL binding (jb_comm_*: no torch.distributed on the data path)
     @staticmethod
     def comm_unique_id():
