@@ -128,7 +128,9 @@ JB_D float quad_pick(float x, unsigned src) {
     const int xi = __builtin_bit_cast(int, x);
     const float x0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0x00, 0xF, 0xF, false)), x1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0x55, 0xF, 0xF, false));
     const float x2 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0xAA, 0xF, 0xF, false)), x3 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0xFF, 0xF, 0xF, false));
-    return src == 0u ? x0 : src == 1u ? x1 : src == 2u ? x2 : x3;
+    // (bit tests, not a chain of `src == k ? ... :` - that becomes a switch on a per-lane value, one exec-masked block per case)
+    const float lo = (src & 1u) ? x1 : x0, hi = (src & 1u) ? x3 : x2;
+    return (src & 2u) ? hi : lo;
 }
 #endif
 

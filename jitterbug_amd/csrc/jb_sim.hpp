@@ -154,7 +154,9 @@ template <typename V> struct LaneConsts {
     V tran0, tran1, tran2, tranm;   // the four per-body-level entries that are picked by a run-time level: kept out of the
                                     // array so that the pick is a select of values, never an indexed access (which would
                                     // force the whole array into scratch memory)
-    JB_HD V tran_of(int level) const { return level == 2 ? tran2 : level == 1 ? tran1 : level == 0 ? tran0 : tranm; }
+    // (a tree of ordered comparisons on purpose: a chain of `level == k ? ... :` is folded into a switch, which a per-lane level turns
+    //  into one exec-masked block per case; these stay three selects)
+    JB_HD V tran_of(int level) const { const V a = level < 1 ? tran0 : tran1, b = level < 3 ? tran2 : tranm; return level < 2 ? a : b; }
     // Split mode (LEAN kernel with one model per env: four 3 KB tables do not fit next to the scratch of eight waves per CU).  Resident in LDS
     // per env (inv, LM_SPLIT_RES floats): the lane-invariant prefix, the pair contact's ellipsoid, and the five per-lane entries that are read
     // after phase A.  Everything else phase A reads comes from the OVERLAY: scratch entries [SC_SYS, SC_SYS + LM_SPLIT_OVL) of the lane - dead
@@ -900,9 +902,13 @@ JB_HD void contact_apply(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const V& 
     auto a1 = lt(rho[0] + mr1, V(0)), a2 = lt(rho[0] - mr1, V(0)), a3 = lt(rho[0] + mr2, V(0)), a4 = lt(rho[0] - mr2, V(0));
     {   // active-set record: exact 5-bit fields for the always-evaluated slots 0..4, a lane-private hash for the rest
         U bits = (mbit(a1) + mbit(a2) * 2u + mbit(a3) * 4u + mbit(a4) * 8u + 16u);
-        if (slot < 5) acc.bw0 = acc.bw0 + selu(valid, bits, zero_u<V>()) * (1u << (5 * slot));
-        else if (slot < 10) acc.bw1 = acc.bw1 + selu(valid, bits, zero_u<V>()) * (1u << (5 * (slot - 5)));
-        else {
+        {   // the two exact words without a lane predicate: a word the slot does not belong to gets a zero added
+            const bool low = slot < 5, leg = slot < 10;
+            const U field = selu(valid, bits, zero_u<V>()) * (leg ? 1u << (5 * (low ? slot : slot - 5)) : 0u);
+            acc.bw0 = acc.bw0 + field * (low ? 1u : 0u);
+            acc.bw1 = acc.bw1 + field * (low ? 0u : 1u);
+        }
+        if (slot >= 10) {
             // (the lane groups' records are ADDED up - contact_sweep: a per-slot odd multiplier keeps a change in one group's slot from
             //  cancelling against the opposite change in another group's, which a plain sum of the 5-bit fields would allow)
             const unsigned sk = (((unsigned)slot * 0x9E3779B1u) ^ (((unsigned)slot * 0x85EBCA6Bu) >> 13)) | 1u;
@@ -1143,7 +1149,8 @@ template <int G, int NG> struct GroupMask {
 };
 // compile-time masks, selected by the (per-lane) group index
 JB_HD unsigned group_mask(int g, int ngroups) {
-    if (ngroups == 4) return g == 0 ? GroupMask<0, 4>::value : g == 1 ? GroupMask<1, 4>::value : g == 2 ? GroupMask<2, 4>::value : GroupMask<3, 4>::value;
+    // (g is a per-lane value: bit tests, which stay selects - a chain of `g == k ? ... :` becomes a switch and one exec-masked block per case)
+    if (ngroups == 4) return (g & 2) ? ((g & 1) ? GroupMask<3, 4>::value : GroupMask<2, 4>::value) : ((g & 1) ? GroupMask<1, 4>::value : GroupMask<0, 4>::value);
     if (ngroups == 2) return g == 0 ? GroupMask<0, 2>::value : GroupMask<1, 2>::value;
     return (1u << NSLOT) - 1u;
 }
