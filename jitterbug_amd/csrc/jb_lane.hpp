@@ -439,6 +439,12 @@ template <typename V> JB_HD Pk2<V> pk_pin(const Pk2<V>& a) { return a; }        
 #if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
 JB_HD Pk2<float> pk_pin(const Pk2<float>& a) { jb_f32x2 r = a.v; asm("" : "+v"(r)); return Pk2<float>(r); }
 #endif
+// ... and a single value: a contact row handed from the registers that built it to the sweep that applies it (jb_sim.hpp contact_sweep)
+// must be the value the row cache holds - a product left open to the sum that follows would be fused into it.
+template <typename V> JB_HD V val_pin(const V& a) { return a; }
+#if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
+JB_HD float val_pin(const float& a) { float r = a; asm("" : "+v"(r)); return r; }
+#endif
 template <typename V> struct lane_traits<Pk2<V>> { using mask = typename lane_traits<V>::mask; using uint = typename lane_traits<V>::uint; using real = typename lane_traits<V>::real; };
 
 // unsigned helpers

@@ -1218,12 +1218,54 @@ template <typename V> JB_HD SpreadPlan<V> make_spread_plan(const LaneScratch<V>&
 // without a contact are not built at all (nobody sums them: contact_apply_leg, rank_one_pass).  Same arithmetic as row_values for a
 // leg slot (level 1 or 2 by the lane's slot).
 template <typename V>
+JB_HD void spread_row_values(const LaneModel<V>& m, const LaneScratch<V>& sc, const SpreadItem<V>& it, const typename lane_traits<V>::uint& me, const Vec3<V>& w,
+                             const Vec3<V>& x, const V& dist, RowVals<V>& r) {
+    using MK = typename lane_traits<V>::mask;
+    const V mu = m.c[LM_MU];
+    auto ldl = [&](int i) { return ld_leg(sc.p, sc.stride, zero_u<V>() + (unsigned)i, it.src, me); };
+    const V thd1 = ldl(SC_ST + 3), thd2 = ldl(SC_ST + 4);
+    const Vec3<V> e1 = v3<V>(ldl(SC_DD + 9), ldl(SC_DD + 10), ldl(SC_DD + 11)), a1 = v3<V>(ldl(SC_DD + 12), ldl(SC_DD + 13), ldl(SC_DD + 14));
+    const Vec3<V> e2 = v3<V>(ldl(SC_DD + 15), ldl(SC_DD + 16), ldl(SC_DD + 17)), a2 = v3<V>(ldl(SC_DD + 18), ldl(SC_DD + 19), ldl(SC_DD + 20));
+    const MK lvl2 = lt_u(it.slot, 5u);
+    const V f_sh = V(1), f_kn = sel(lvl2, V(1), V(0));
+    const V tran = sel(lvl2, quad_pick(m.c.tran2, it.src), quad_pick(m.c.tran1, it.src));
+    const MK valid = lt(dist, V(0));
+    const V imp = impedance(m, dist);
+    const V invD = (V(1) - imp) * (tran * ((V(1) + m.c[LM_FR2]) * (V(2) * mu * mu)));
+    r.x = x;
+    r.D = sel(valid, imp * vrcp(invD), V(0));
+    const V jdot = f_kn * thd2;
+    const Vec3<V> p1 = cross(e1, x - a1), p2 = cross(e2, x - a2);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const Vec3<V> d = sc.ld3(SC_DD + 3 * k);
+        const Vec3<V> ang = cross(x, d);
+        const V jsh = f_sh * dot(d, p1);
+        const V j7 = f_kn * dot(d, p2);
+        const V vel = dot(ang, w) + sc.ld(SC_DD + 21 + k) + jsh * thd1 + j7 * jdot;
+        V ah = -m.c[LM_BB] * vel;
+        if (k == 0) ah = ah - m.c[LM_KK] * imp * dist;
+        r.jsh[k] = jsh; r.j7[k] = j7; r.ah[k] = ah;
+    }
+}
+// ... into the row cache of the contact's leg (the weight takes the distance's place)
+template <typename V>
+JB_HD void spread_row_store(const LaneScratch<V>& sc, const SpreadItem<V>& it, const typename lane_traits<V>::uint& me, const typename lane_traits<V>::uint& e0, const RowVals<V>& r) {
+    st_leg(sc.p, sc.stride, e0 + 3u, it.src, me, r.D, it.valid);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        st_leg(sc.p, sc.stride, e0 + (unsigned)(4 + k), it.src, me, r.jsh[k], it.valid);
+        st_leg(sc.p, sc.stride, e0 + (unsigned)(7 + k), it.src, me, r.j7[k], it.valid);
+        st_leg(sc.p, sc.stride, e0 + (unsigned)(10 + k), it.src, me, r.ah[k], it.valid);
+    }
+}
+// the spread slots' rows in a pass of their own (the reference form, JB_SEPARATE_ROW_BUILD, and a variant whose layout says so: the
+// product builds them inside the first full sweep - contact_sweep)
+template <typename V>
 JB_HD void contact_rows_build_spread(const LaneModel<V>& m, const LaneScratch<V>& sc, const SlotPlan& plan, const SpreadPlan<V>& sp) {
     using U = typename lane_traits<V>::uint;
-    using MK = typename lane_traits<V>::mask;
     const U me = quad_lane_id((const V*)nullptr);
     const Vec3<V> w = sc.ld3(SC_ST);
-    const V mu = m.c[LM_MU];
 #pragma unroll 1
     for (int r = 0;; r++) {
         const SpreadItem<V> it = r == 0 ? sp.item0 : spread_assign<V>(sp.own, sp.mg, r);
@@ -1231,39 +1273,15 @@ JB_HD void contact_rows_build_spread(const LaneModel<V>& m, const LaneScratch<V>
         const U e0 = popc_u(and_u(below, zero_u<V>() + plan.live)) * (unsigned)ROW_F + (unsigned)SC_ROWS;
         const Vec3<V> x = v3<V>(ld_leg(sc.p, sc.stride, e0, it.src, me), ld_leg(sc.p, sc.stride, e0 + 1u, it.src, me), ld_leg(sc.p, sc.stride, e0 + 2u, it.src, me));
         const V dist = ld_leg(sc.p, sc.stride, e0 + 3u, it.src, me);
-        auto ldl = [&](int i) { return ld_leg(sc.p, sc.stride, zero_u<V>() + (unsigned)i, it.src, me); };
-        const V thd1 = ldl(SC_ST + 3), thd2 = ldl(SC_ST + 4);
-        const Vec3<V> e1 = v3<V>(ldl(SC_DD + 9), ldl(SC_DD + 10), ldl(SC_DD + 11)), a1 = v3<V>(ldl(SC_DD + 12), ldl(SC_DD + 13), ldl(SC_DD + 14));
-        const Vec3<V> e2 = v3<V>(ldl(SC_DD + 15), ldl(SC_DD + 16), ldl(SC_DD + 17)), a2 = v3<V>(ldl(SC_DD + 18), ldl(SC_DD + 19), ldl(SC_DD + 20));
-        const MK lvl2 = lt_u(it.slot, 5u);
-        const V f_sh = V(1), f_kn = sel(lvl2, V(1), V(0));
-        const V tran = sel(lvl2, quad_pick(m.c.tran2, it.src), quad_pick(m.c.tran1, it.src));
-        const MK valid = lt(dist, V(0));
-        const V imp = impedance(m, dist);
-        const V invD = (V(1) - imp) * (tran * ((V(1) + m.c[LM_FR2]) * (V(2) * mu * mu)));
-        const V D = sel(valid, imp * vrcp(invD), V(0));
-        const V jdot = f_kn * thd2;
-        const Vec3<V> p1 = cross(e1, x - a1), p2 = cross(e2, x - a2);
-        st_leg(sc.p, sc.stride, e0 + 3u, it.src, me, D, it.valid);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const Vec3<V> d = sc.ld3(SC_DD + 3 * k);
-            const Vec3<V> ang = cross(x, d);
-            const V jsh = f_sh * dot(d, p1);
-            const V j7 = f_kn * dot(d, p2);
-            const V vel = dot(ang, w) + sc.ld(SC_DD + 21 + k) + jsh * thd1 + j7 * jdot;
-            V ah = -m.c[LM_BB] * vel;
-            if (k == 0) ah = ah - m.c[LM_KK] * imp * dist;
-            st_leg(sc.p, sc.stride, e0 + (unsigned)(4 + k), it.src, me, jsh, it.valid);
-            st_leg(sc.p, sc.stride, e0 + (unsigned)(7 + k), it.src, me, j7, it.valid);
-            st_leg(sc.p, sc.stride, e0 + (unsigned)(10 + k), it.src, me, ah, it.valid);
-        }
+        RowVals<V> rv;
+        spread_row_values<V>(m, sc, it, me, w, x, dist, rv);
+        spread_row_store<V>(sc, it, me, e0, rv);
         if (!any_lane(it.more)) break;
     }
 }
 
-// y-independent rows of the live slots, once per substep (slots beyond the cache keep their candidate only; their rows are
-// recomputed in registers in every pass)
+// y-independent rows of the live slots in a pass of their own, once per substep (slots beyond the cache keep their candidate only; their
+// rows are recomputed in registers in every pass).  Only where SimOpts::fuse_rows is off: otherwise the first full sweep builds them.
 template <typename V, bool PAIR = false>
 JB_HD void contact_rows_build_all(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xtra, const SlotPlan& plan, const SpreadPlan<V>& sp) {
     if (!plan.grouped && sc.grp != 0) return;
@@ -1283,8 +1301,11 @@ JB_HD void contact_rows_build_all(const LaneModel<V>& m, const LaneScratch<V>& s
 // every live candidate slot against the iterate y kept in the scratch (SC_Y); with helper groups the partial sums of the
 // groups are combined by cross-lane exchanges so that every group ends with the complete accumulator
 // (returns the number of spread rounds it made: diagnostics only)
+// build (wave-uniform; the first full sweep of a substep's hot solve): the cached rows do not exist yet - a lane forms the row of the
+// contact it has in a round from the candidate phase A left (row_values / spread_row_values), stores it for every later pass and applies
+// the values it holds.  The lane that builds a row is the lane that sweeps it, here and in every later sweep: both walk the same plan.
 template <typename V, bool PAIR = false, bool LS = false>
-JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xtra, const SlotPlan& plan, const SpreadPlan<V>& sp, int mode, const Vec3<V> (&dk)[3], NewtonAcc<V>& acc, const bool zero_g1 = false) {
+JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xtra, const SlotPlan& plan, const SpreadPlan<V>& sp, int mode, const Vec3<V> (&dk)[3], NewtonAcc<V>& acc, const bool zero_g1 = false, const bool build = false) {
     // zero_g1 (SimOpts::offload): group 1 must leave with an all-zero accumulator - it factorises M + h diag(b)
     // with the instruction stream that factorises the main lanes' Newton system (substep_impl)
     const bool g1z = zero_g1 && sc.grp == 1;
@@ -1313,6 +1334,8 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
         // spread rounds over the leg slots (normally one): every lane of the quad works on a contact of its env, whichever leg it sits on
         using U = typename lane_traits<V>::uint;
         const U me = quad_lane_id((const V*)nullptr);
+        Vec3<V> wst = v3<V>(V(0), V(0), V(0));
+        if (build) wst = sc.ld3(SC_ST);
 #pragma unroll 1
         for (int r = 0;; r++) {
             const SpreadItem<V> it = r == 0 ? sp.item0 : spread_assign<V>(sp.own, sp.mg, r);
@@ -1320,11 +1343,22 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
             const U e0 = popc_u(and_u(below, zero_u<V>() + plan.live)) * (unsigned)ROW_F + (unsigned)SC_ROWS;      // the slot's cached row: entry = rank among the live slots
             RowVals<V> rv;
             rv.x = v3<V>(ld_leg(sc.p, sc.stride, e0, it.src, me), ld_leg(sc.p, sc.stride, e0 + 1u, it.src, me), ld_leg(sc.p, sc.stride, e0 + 2u, it.src, me));
-            rv.D = ld_leg(sc.p, sc.stride, e0 + 3u, it.src, me);
+            rv.D = ld_leg(sc.p, sc.stride, e0 + 3u, it.src, me);      // (building: the candidate's effective distance, still)
+            if (build) {
+                // (a lane without a contact this round forms a row from whatever its entry holds and stores nothing: contact_apply_leg's
+                //  selects keep it out of the sums)
+                RowVals<V> rb;
+                spread_row_values<V>(m, sc, it, me, wst, rv.x, rv.D, rb);
+                spread_row_store<V>(sc, it, me, e0, rb);
+                rv.D = val_pin(rb.D);
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                rv.jsh[k] = ld_leg(sc.p, sc.stride, e0 + (unsigned)(4 + k), it.src, me); rv.j7[k] = ld_leg(sc.p, sc.stride, e0 + (unsigned)(7 + k), it.src, me);
-                rv.ah[k] = ld_leg(sc.p, sc.stride, e0 + (unsigned)(10 + k), it.src, me);
+                for (int k = 0; k < 3; k++) { rv.jsh[k] = val_pin(rb.jsh[k]); rv.j7[k] = val_pin(rb.j7[k]); rv.ah[k] = val_pin(rb.ah[k]); }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    rv.jsh[k] = ld_leg(sc.p, sc.stride, e0 + (unsigned)(4 + k), it.src, me); rv.j7[k] = ld_leg(sc.p, sc.stride, e0 + (unsigned)(7 + k), it.src, me);
+                    rv.ah[k] = ld_leg(sc.p, sc.stride, e0 + (unsigned)(10 + k), it.src, me);
+                }
             }
             V yls[2];
             yls[0] = ld_leg(sc.p, sc.stride, zero_u<V>() + (unsigned)(SC_Y + 6), it.src, me); yls[1] = ld_leg(sc.p, sc.stride, zero_u<V>() + (unsigned)(SC_Y + 7), it.src, me);
@@ -1345,8 +1379,25 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
         const int slot = lane_on ? mine : __builtin_ctz(sp.on ? (plan.live & ~sp.slots) : plan.live);       // idle lanes read some BUILT entry (spread mode: one of this loop's) and contribute nothing
         const int rank = plan_rank(plan, slot);
         RowVals<V> rv;
-        if (rank < ROW_K) row_load<V>(sc, rank, rv);
-        else {      // beyond the cache: the candidate -> row values, every pass
+        if (rank < ROW_K) {
+            if (build) {
+                // An idle lane's entry may not be built yet (its owner builds it in this very sweep): the position is there, the rest of
+                // its row is zeros by selects - no weight times whatever the entry holds - and what stands for its distance is read from
+                // the position, which nobody writes here.
+                const int e0 = SC_ROWS + ROW_F * rank;
+                RowVals<V> rb;
+                row_values<V, PAIR>(m, sc, xtra, slot, sc.ld3(e0), sc.ld(e0 + (lane_on ? 3 : 0)), rb);
+                if (lane_on) {
+                    sc.st(e0 + 3, rb.D);
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { sc.st(e0 + 4 + k, rb.jsh[k]); sc.st(e0 + 7 + k, rb.j7[k]); sc.st(e0 + 10 + k, rb.ah[k]); }
+                }
+                rv.x = rb.x;
+                rv.D = lane_on ? val_pin(rb.D) : V(0);
+#pragma unroll
+                for (int k = 0; k < 3; k++) { rv.jsh[k] = lane_on ? val_pin(rb.jsh[k]) : V(0); rv.j7[k] = lane_on ? val_pin(rb.j7[k]) : V(0); rv.ah[k] = lane_on ? val_pin(rb.ah[k]) : V(0); }
+            } else row_load<V>(sc, rank, rv);
+        } else {      // beyond the cache: the candidate -> row values, every pass
             const int c0 = 4 * (rank - ROW_K) * sc.ovc_stride;
             row_values<V, PAIR>(m, sc, xtra, slot, v3<V>(sc.ovc[c0], sc.ovc[c0 + sc.ovc_stride], sc.ovc[c0 + 2 * sc.ovc_stride]), sc.ovc[c0 + 3 * sc.ovc_stride], rv);
         }
@@ -1702,6 +1753,8 @@ struct SimOpts {
                          //    very instructions that compute the legs, and handed over with 23 cross-lane swaps (group 0 <- 2, group 1 <- 3).
     int spread = 1;      // 1: a plan with more than one round sweeps the leg slots in spread mode (lanes of idle legs adopt contacts of a leg that has
                          //    several: "spread sweeps" below); 0: diagnostic, the ordinary sweep only
+    int fuse_rows = 1;   // 1: the contact rows are built by the first full sweep of the substep's hot solve (contact_sweep `build`); 0: in a pass of
+                         //    their own before it (StepLayout::fused_row_build: the variants that would spill).  Same arithmetic, same bits.
     float* capture = nullptr;           // diagnostic builds (-DJB_CAPTURE): ring of JB_CAPTURE_SLOTS records x 64 floats - the entry state of substeps whose contact solve stayed
     unsigned* capture_count = nullptr;  //   unconverged after the line-searched pass (substep_impl), and how many there were
     unsigned long long* prof;   // diagnostic builds: per-wave cycle accumulators [phaseA, check sweeps, full sweeps, solves, integrate]
@@ -1925,7 +1978,7 @@ inline void ls_trace_check(int it, const Mask4& unc, const UQuad& b0, const UQua
 template <typename V, bool PAIR, bool LS>
 JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>& s, const SimOpts& o, const bool xtra, const SlotPlan& plan, const SpreadPlan<V>& spl,
                         const Mat3<V>& Rw, StarSys<V>& sys, const Vec3<V> (&dk)[3], const bool any_contact, const typename lane_traits<V>::mask& env_con,
-                        Pk2<V> (&yr)[3], V (&yl)[2], V& ym, typename lane_traits<V>::mask& capped) {
+                        Pk2<V> (&yr)[3], V (&yl)[2], V& ym, typename lane_traits<V>::mask& capped, const bool build_rows = false) {
     using MK = typename lane_traits<V>::mask;
     using U = typename lane_traits<V>::uint;
     using W = Pk2<V>;
@@ -1987,7 +2040,7 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
             for (;;) {
                 // ---- full pass (reads the iterate of the last check from the scratch: rank-one results are stored only after this pass)
                 if (any_contact) {
-                    const int sweep_rounds = contact_sweep<V, PAIR, LS>(m, sc, xtra, plan, spl, 0, dk, acc, have_dfac);
+                    const int sweep_rounds = contact_sweep<V, PAIR, LS>(m, sc, xtra, plan, spl, 0, dk, acc, have_dfac, !LS && build_rows && it == 0);
                     (void)sweep_rounds;
                     prev_bw0 = acc.bw0; prev_bw1 = acc.bw1; prev_xh = acc.xh;
                     JB_PROF_ADD(o, 2);
@@ -2662,18 +2715,26 @@ JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
     const SpreadPlan<V> spl = make_spread_plan<V>(sc, plan, o.spread != 0 && any_contact);
 
     // ================= phase B: contact solve (primal Newton on the active set) and final acceleration: newton_phase above.
-    // The y-independent rows of the live contacts are built ONCE per substep; the solve may run twice.
+    // The y-independent rows of the live contacts are built ONCE per substep, by the first full sweep of the hot solve (contact_sweep's
+    // `build`: the lane that sweeps a row forms it, stores it and applies the registers it holds - no pass of its own, no store-and-reload
+    // on the substep's critical path); the solve may run twice, the second time on the cached rows.
+    // JB_SEPARATE_ROW_BUILD: the reference form, a pass of its own before the solve (A/B measurements and tests/test_fused_row_build_cpu.py).
+#ifdef JB_SEPARATE_ROW_BUILD
+    const bool fused_rows = false;
+#else
+    const bool fused_rows = o.fuse_rows != 0;
+#endif
     Vec3<V> dk[3];
     if (any_contact) {
 #pragma unroll
         for (int k = 0; k < 3; k++) dk[k] = sc.ld3(SC_DD + 3 * k);      // contact-frame directions: once per substep, every lane
-        contact_rows_build_all<V, PAIR>(m, sc, xtra, plan, spl);
+        if (!fused_rows) contact_rows_build_all<V, PAIR>(m, sc, xtra, plan, spl);
         JB_PROF_ADD(o, 5);
     }
     Pk2<V> yrp[3];
     V yl[2], ym;
     MK capped = lt(V(1), V(0));        // main lanes: this env's iteration ran into the cap
-    bool redone = newton_phase<V, PAIR, false>(m, sc, s, o, xtra, plan, spl, Rw, sys, dk, any_contact, env_con, yrp, yl, ym, capped);
+    bool redone = newton_phase<V, PAIR, false>(m, sc, s, o, xtra, plan, spl, Rw, sys, dk, any_contact, env_con, yrp, yl, ym, capped, fused_rows);
 #ifdef JB_NO_RESOLVE      // A/B measurements only: the hot instantiation alone (a capped substep keeps its last iterate and is not counted)
     redone = false;
 #endif

@@ -28,6 +28,9 @@ struct StepLayout {
     bool red_lds;            // LaneScratch::red_lds; also: the overflow candidates sit in the scratch (false: in the global block below)
     int ovc_floats;          // floats per main lane of the wave's block in global memory (0: none)
     int waves_per_simd;      // resident waves per SIMD (the register budget the kernel is compiled for)
+    bool fused_row_build;    // the first full Newton sweep of a substep builds the contact rows it applies (SimOpts::fuse_rows); false: the rows are
+                             // built in a pass of their own before the solve - the rows whose register budget the fused sweep does not fit (it
+                             // adds scratch operations to their substep loop's hot part: tools/asm_spills.py).  Same bits either way.
 };
 
 constexpr StepLayout step_layout(int epw, bool lean, bool pair) {
@@ -46,6 +49,7 @@ constexpr StepLayout step_layout(int epw, bool lean, bool pair) {
     l.red_lds = !lean;
     l.ovc_floats = lean ? OVC_FLOATS_PER_LANE : 0;
     l.waves_per_simd = lean ? 2 : 1;
+    l.fused_row_build = !(lean && pair) && !(pair && epw == 1) && !(!pair && !lean && epw == 8);
     return l;
 }
 
@@ -118,7 +122,7 @@ template <typename V> JB_HD void helper_lane_state(LaneState<V>& s) {
 JB_HD SimOpts sim_opts(const StepLayout& l, int contacts, int max_newton, int implicit_damp, int rank_one, int spread) {
     SimOpts o;
     o.contacts = contacts; o.max_newton = max_newton; o.implicit_damp = implicit_damp; o.rank_one = rank_one; o.spread = spread;
-    o.lean = l.lean ? 1 : 0; o.offload = l.offload ? 1 : 0; o.aux = l.aux ? 1 : 0;
+    o.lean = l.lean ? 1 : 0; o.offload = l.offload ? 1 : 0; o.aux = l.aux ? 1 : 0; o.fuse_rows = l.fused_row_build ? 1 : 0;
     o.prof = nullptr; o.hist = nullptr;
     return o;
 }

@@ -35,7 +35,11 @@ S = K * 50.0
 cyc = b[:, 0] / S
 print("fused rollout, %d envs, K = %d, %s actions, instrumented build: cycles per substep (s_memtime) mean %.0f median %.0f p99 %.0f max %.0f; mean/max %.3f" % (
     n, K, mode, cyc.mean(), np.median(cyc), np.quantile(cyc, .99), cyc.max(), cyc.mean() / cyc.max()))
-hdr = "cycles/substep | A check-sweeps full-sweeps solve-tail integrate | rows-build star-solves logic | checks fulls rank-one per substep | live slots per contact substep | all-geom substep share"
+# prof[4] ("B+C"): everything from the end of the rows-build bucket to the end of phase C - the whole Newton phase (its own buckets: check-sweeps,
+# full-sweeps, solve-tail, star-solves, logic) plus the integration, not the integration alone.
+# rows-build (prof[5]): the contact-frame loads and, in a separate-pass build (-DJB_SEPARATE_ROW_BUILD, or a variant whose layout keeps the pass),
+# the row build; the product builds the rows inside the first full sweep of a substep, and those cycles are counted under full-sweeps.
+hdr = "cycles/substep | A check-sweeps full-sweeps solve-tail B+C | rows-build star-solves logic | checks fulls rank-one per substep | live slots per contact substep | all-geom substep share"
 def row(x):
     return "%6.0f | %5.0f %5.0f %5.0f %5.0f %5.0f | %5.0f %5.0f %5.0f | %.2f %.2f %.2f | %.2f | %.2f" % (
         x[0] / S, x[4] / S, x[5] / S, x[6] / S, x[7] / S, x[8] / S, x[12] / S, x[13] / S, x[14] / S, x[9] / S, x[2] / S, x[15] / S, x[11] / max(x[3], 1), x[1] / S)
