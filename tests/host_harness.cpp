@@ -234,6 +234,47 @@ extern "C" int jbh_rollout(const double* P, double* qpos, double* qvel, double* 
     return use_float ? rollout<float>(P, qpos, qvel, target, counters, K, actions, task, nsub, step_limit, auto_reset, random_pose, seed, env_global, policy_params, ngroups, rows_out)
                      : rollout<double>(P, qpos, qvel, target, counters, K, actions, task, nsub, step_limit, auto_reset, random_pose, seed, env_global, policy_params, ngroups, rows_out);
 }
+// ---- the task layer alone (jb_task.hpp observe / reward / reward_terms / heuristic_policy) on n states, T = double or float: each state
+// goes through the words the device holds (state_from_qpos: T-rounded root state, wrapped motor angle) and core_from_lane_state, as in the
+// kernels.  out [n, 25] = [obs(19, zeros beyond the task's width) | reward | P, H, V, U | action of the heuristic policy on that row]
+template <typename T>
+static int task_layer(const double* P, int task, int n, const double* qpos, const double* qvel, const double* target, const double* policy_params, double* out) {
+    using V = Quad<T>;
+    HostRun<T> w;
+    if (int rc = w.init(P, 1, false, false, 1, 12, 1, 1)) return rc;
+    PolicyParams<T> pp = default_policy_params<T>();
+    if (policy_params) { pp.kick_angle = T(policy_params[0]); pp.speed = T(policy_params[1]); pp.angle_threshold = T(policy_params[2]); }
+    const T target_z = lane0(w.m.c[LM_TARGET_Z]);
+    for (int i = 0; i < n; i++) {
+        const LaneState<V> s = state_from_qpos<T>(qpos + (size_t)i * 16, qvel + (size_t)i * 15);
+        const T tgt[3] = {T(target[3 * i]), T(target[3 * i + 1]), T(target[3 * i + 2])};
+        EnvCore<T> e;
+        core_from_lane_state<V>(w.m, s, tgt, e);
+        T obs[19], terms[4];
+        observe<T>(task, e, target_z, obs, 1);
+        reward_terms<T>(e, target_z, terms);
+        double* o = out + (size_t)i * 25;
+        for (int j = 0; j < 19; j++) o[j] = j < obs_dim(task) ? (double)obs[j] : 0.0;
+        o[19] = (double)reward<T>(task, e, target_z);
+        for (int j = 0; j < 4; j++) o[20 + j] = (double)terms[j];
+        o[24] = (double)heuristic_policy<T>(task, obs, 1, pp);
+    }
+    return 0;
+}
+extern "C" int jbh_task_layer(const double* P, int task, int n, const double* qpos, const double* qvel, const double* target, const double* policy_params, int use_float, double* out) {
+    return use_float ? task_layer<float>(P, task, n, qpos, qvel, target, policy_params, out) : task_layer<double>(P, task, n, qpos, qvel, target, policy_params, out);
+}
+// heuristic_policy<float> on n given observation rows [n, obs_dim(task)] (what jb_policy_device computes)
+extern "C" void jbh_policy_rows(int task, int n, const double* obs, const double* policy_params, double* action) {
+    PolicyParams<float> pp = default_policy_params<float>();
+    if (policy_params) { pp.kick_angle = float(policy_params[0]); pp.speed = float(policy_params[1]); pp.angle_threshold = float(policy_params[2]); }
+    const int D = obs_dim(task);
+    for (int i = 0; i < n; i++) {
+        float row[19] = {0};
+        for (int j = 0; j < D; j++) row[j] = (float)obs[(size_t)i * D + j];
+        action[i] = (double)heuristic_policy<float>(task, row, 1, pp);
+    }
+}
 // ONE substep from a captured fp32 record (jb_sim.hpp SimOpts::capture: the substep's entry state with its warm start, 64 floats), main lanes +
 // three helper groups; returns the failure counter's increment.  trace = 1 prints the line-searched iteration.
 extern "C" int jbh_substep_record(const double* P, const float* rec, int max_newton, int ngroups, int trace, double* fail_out) {

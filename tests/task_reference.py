@@ -1,0 +1,501 @@
+"""The task layer (jitterbug_amd/csrc/jb_task.hpp: observation, reward, the four reward terms, the heuristic policy) against fp64, shared by
+tests/test_task_layer_host.py (the source on the host), tests/test_gpu_task_seams.py (the kernels) and the parity protocol of
+tests/test_gpu_parity.py.  Not a conftest: plain helpers.
+
+REFERENCE.  oracle.observation / oracle.reward / oracle.reward_terms in fp64, heuristic_policies.policy_batch for actions, always evaluated
+on the state AS THE DEVICE HOLDS IT (get_state() after set_state() or after a step), so that rounding the inputs is not part of a comparison.
+
+BOUND.  Every compared value y gets
+
+    bound(y) = C * 2^-24 * (|y| + S) + 2^-23 * S,        S = sum_i |dy/dx_i| * |x_i|
+
+where the x_i are the fp32 words the formula reads - the state words and the formula's own constants (pi/2, 2 pi, 0.1, 1 ...: the kernel
+holds them rounded, and a result near zero still carries their rounding) -, S is propagated through the formula by the chain rule with
+absolute values (`_M` below: a sum adds the S of its operands, a product a*b gives |a| S_b + |b| S_a, a function multiplies by its slope), C
+is the number of roundings on the longest chain of the formula as jb_task.hpp writes it (the bound also carries the format's underflow,
+(C + 1) * 2^-116, see UNDERFLOW: it matters only for words below 1e-38), and the second term is the input term: one ulp
+(at most 2^-23 relative) on every word - what get_state()'s fp64 hi + lo height and quaternion differ by from the hi words the task layer reads.
+Nothing in it is fitted.  The slopes are closed forms:
+    position term  0.1^((20 d)^2)          |dP/dd| = P * 2 ln10 * 400 d          at most 1.302 * 20 per metre
+    upright term   0.1^((2 (1 - Rzz))^2)   |dU/dRzz| = U * 2 ln10 * 4 |1 - Rzz|  at most 1.302 * 2 per unit of Rzz
+    heading term   (1 + cos 2a) / 2        |dH/da| = |sin 2a|                    at most 1 per radian; 0 beyond |a| = pi/2
+    velocity term  clamp(10 v, 0, 1)       10 per m/s between its clamps, 0 on them
+    yaw            atan2(R10, R00)         1 / hypot(R00, R10) per unit of each of the two matrix entries
+    distance       |R^T (t - p)|           unit gradient: S_d = sqrt(S_0^2 + S_1^2 + S_2^2) of the three components
+ROUNDING COUNTS (C, counted by `_M` along the formula and pinned by ROUNDINGS, which the host test asserts).  One per +, -, *, /, sqrt and
+per constant that is not exact in fp32; exact scalings (0.5, 2) count nothing; library routines by their accuracy: atan2f 3, expf 2, the
+quarter-turn sine / cosine 2.  A matrix entry w w + x x - y y - z z is 4 (product, three sums), 2 (x y + w z) is 2:
+    obs 0-1, 3-9   0 (copies, an exact halving)            obs 2  2 (pz * 20 - 1)         obs 10-12, 14  2 (constant 1/35, 1/180; product)
+    obs 13         5 (phi + pi/2: 2 with the constant; wrap: + k 2 pi, guard: 2; / pi: 1)
+    angle / pi     12 (R00 4, atan2f 3, - pi/2 1, tyaw - yaw 1, wrap 2, / pi 1; the target's own chain is shorter: 2 + 2 + 3)
+    target in body 8, 8, 7 (t - p 1 | R 4; product 1; two sums 2; the scaling 1 - the z component sums its long product last)
+    velocity in target frame 10, 10, 6 (R 4, * l 1, three sums 3; product with the cosine 1, sum 1 - the z component is the sensor's own)
+    P 16 (components 7, square 1, two sums 2, sqrt 1, * 20 1, * ln 0.1 twice 2, expf 2)      U 9 (Rzz 4, 1 - 1, square 1, * ln 0.1 1, expf 2)
+    H 16 (angle 11, / (pi/2) 1, * pi 1, cosine 2, 1 + 1)          V 13 (forward speed 10, 0.1 - v 1, * 10 1, 1 - 1)
+    reward: the term(s) it multiplies, + 1 per product, + 1 for 1 - P: 18, 17, 14, 17, 18 for the five tasks
+CAP ON THE BOUND (a condition on a state set, checked by `assert_cap`, so that the bound cannot be vacuous): at most 1e-5 - the suite's strict
+absolute line - on every state outside the near-vertical family, at most 1e-5 / hypot(R00, R10) inside it.
+REFERENCE'S OWN ERROR: 2^-51 * (1 + |y|), see REFERENCE.
+ANGLES.  The normalised angle entries (obs[13]; obs[15] or obs[18] where the task has them) are discontinuous at +-1 and are compared by circular
+distance min(|d|, 2 - |d|); everything else directly."""
+import ctypes as C
+
+import numpy as np
+
+from jitterbug_amd import heuristic_policies as hp
+from jitterbug_amd import model
+
+U24 = 2.0 ** -24
+# below the smallest normal fp32 number, 2^-126, a word may read as zero (flush to zero) in any of the C + 1 steps of a chain; no slope of these
+# formulas reaches 2^10 (the steepest: the position term per unit of a body-frame component, 1.302 * 20 * 20 = 521)
+UNDERFLOW = 2.0 ** -116
+# the reference's own error: the oracle normalises an entry as (v - lo) / (hi - lo) * 2 - 1 in fp64, four roundings at magnitude 1 + |y|
+REFERENCE = 2.0 ** -51
+PI = np.pi
+ANGLE_ENTRIES = dict(move_from_origin=(13,), face_direction=(13, 15), move_in_direction=(13, 15), move_to_position=(13,), move_to_pose=(13, 18))
+STRICT_ABS = 1e-5
+
+
+class _M:
+    """value, S (see the module docstring) and the roundings on the longest chain, through one formula; arrays over the states"""
+
+    def __init__(self, val, s=None, c=0):
+        self.val = np.asarray(val, dtype=np.float64)
+        self.s = np.abs(self.val) if s is None else np.broadcast_to(np.asarray(s, dtype=np.float64), self.val.shape)
+        self.c = c
+
+    @staticmethod
+    def const(x, exact=False):
+        """a constant of the formula: a word the kernel reads like any other (S = |x|); one rounding unless fp32 holds it exactly"""
+        return _M(np.float64(x), abs(x), 0 if exact else 1)
+
+    def _lift(self, o):
+        return o if isinstance(o, _M) else _M.const(o, exact=float(np.float32(o)) == float(o))
+
+    def __add__(self, o):
+        o = self._lift(o)
+        return _M(self.val + o.val, self.s + o.s, max(self.c, o.c) + 1)
+
+    def __sub__(self, o):
+        o = self._lift(o)
+        return _M(self.val - o.val, self.s + o.s, max(self.c, o.c) + 1)
+
+    def __rsub__(self, o):
+        return self._lift(o) - self
+
+    def __mul__(self, o):
+        o = self._lift(o)
+        return _M(self.val * o.val, np.abs(self.val) * o.s + np.abs(o.val) * self.s, max(self.c, o.c) + 1)
+
+    def __truediv__(self, o):
+        o = self._lift(o)
+        return _M(self.val / o.val, self.s / np.abs(o.val) + np.abs(self.val) * o.s / o.val ** 2, max(self.c, o.c) + 1)
+
+    def scaled(self, k):
+        """an exact scaling (a power of two): no rounding"""
+        return _M(self.val * k, self.s * abs(k), self.c)
+
+    def fn(self, val, slope, roundings):
+        return _M(val, np.abs(slope) * self.s, self.c + roundings)
+
+    def bound(self):
+        return U24 * (self.c * (np.abs(self.val) + self.s)) + 2 * U24 * self.s + (self.c + 1) * UNDERFLOW + REFERENCE * (1.0 + np.abs(self.val))
+
+
+def _rot(q):
+    w, x, y, z = q
+    two = lambda m: m.scaled(2.0)
+    return [[w * w + x * x - y * y - z * z, two(x * y - w * z), two(x * z + w * y)],
+            [two(x * y + w * z), w * w - x * x + y * y - z * z, two(y * z - w * x)],
+            [two(x * z - w * y), two(y * z + w * x), w * w - x * x - y * y + z * z]]
+
+
+def _wrap(a):
+    """wrap_pi: a + k 2 pi (one constant, one sum; the product is exact for the k it meets here and counted with the constant), and a guard"""
+    k = np.floor((PI - a.val) / (2 * PI))
+    return _M(a.val + 2 * PI * k, a.s + 2 * PI * np.abs(k), a.c + 2)
+
+
+def _formulas(P, q, v, t):
+    """every quantity of jb_task.hpp on the states (q [N,16], v [N,15], t [N,3], fp64 as the device reports them) as _M"""
+    q, v, t = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (q, v, t))
+    P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+    inp = lambda a: _M(a)
+    px, py, pz = inp(q[:, 0]), inp(q[:, 1]), inp(q[:, 2])
+    quat = [inp(q[:, 3 + i]) for i in range(4)]
+    k = np.floor((q[:, 15] + PI) / (2 * PI))
+    phi, phid = inp(q[:, 15] - 2 * PI * k), inp(v[:, 14])
+    vel, w = [inp(v[:, i]) for i in range(3)], [inp(v[:, 3 + i]) for i in range(3)]
+    tx, ty, tpsi = inp(t[:, 0]), inp(t[:, 1]), inp(t[:, 2])
+    c0 = [inp(P[:, model.P_BODY + model.B_COM + i]) for i in range(3)]
+    target_z = inp(P[:, model.P_TARGETZ])
+    R = _rot(quat)
+    f = {}
+    f["direct"] = [px.scaled(0.5), py.scaled(0.5), pz * 20.0 - 1.0] + quat + vel + [wi * (1.0 / 35) for wi in w]
+    f["motor"] = _wrap(phi + PI / 2) / PI
+    f["motor_vel"] = phid * (1.0 / 180)
+    # angle to the target: atan2(R10, R00) - pi/2 against the target's yaw (its own chain - half angle, sine / cosine, c c - s s, atan2f - is shorter
+    # and its slope in tpsi is 1)
+    h = np.hypot(R[0][0].val, R[1][0].val)
+    yaw = _M(np.arctan2(R[1][0].val, R[0][0].val), (R[0][0].s + R[1][0].s) / h, max(R[0][0].c, R[1][0].c) + 3) - PI / 2
+    tyaw = _M(np.arctan2(np.sin(t[:, 2]), np.cos(t[:, 2])), np.abs(t[:, 2]), 2 + 2 + 3)
+    ang = _wrap(tyaw - yaw)
+    f["h"], f["angle"], f["angle_obs"] = h, ang, ang / PI
+    # target in the body frame, distance
+    d3 = [tx - px, ty - py, target_z - pz]
+    tb = [R[0][i] * d3[0] + R[1][i] * d3[1] + R[2][i] * d3[2] for i in range(3)]
+    f["target_body"] = [tb[0] * (1.0 / 3), tb[1] * (1.0 / 3), tb[2] * 10.0]
+    dist = _M(np.sqrt(sum(c.val ** 2 for c in tb)), np.sqrt(sum(c.s ** 2 for c in tb)), max(c.c for c in tb) + 1 + 2 + 1)
+    # velocity of the root body's own centre of mass in the target frame
+    l = [w[1] * c0[2] - w[2] * c0[1], w[2] * c0[0] - w[0] * c0[2], w[0] * c0[1] - w[1] * c0[0]]
+    fl = [vel[i] + R[i][0] * l[0] + R[i][1] * l[1] + R[i][2] * l[2] for i in range(3)]
+    ct, st = tpsi.fn(np.cos(t[:, 2]), np.sin(t[:, 2]), 2), tpsi.fn(np.sin(t[:, 2]), np.cos(t[:, 2]), 2)
+    vt = [ct * fl[0] + st * fl[1], ct * fl[1] - st * fl[0], fl[2]]
+    f["vel_target"] = vt
+    # the four terms
+    LN10 = np.log(10.0)
+    dn = dist * 20.0
+    arg = dn * dn * LN10
+    Pt = arg.fn(np.exp(-arg.val), np.exp(-arg.val), 2)
+    du = (1.0 - R[2][2]).scaled(2.0)
+    argu = du * du * LN10
+    Ut = argu.fn(np.exp(-argu.val), np.exp(-argu.val), 2)
+    x = ang.fn(np.abs(ang.val), 1.0, 0) / (PI / 2)
+    inside = x.val < 1.0
+    cosx = (x * PI).fn(np.cos(PI * x.val), np.sin(PI * x.val), 2)
+    Hf = (cosx + 1.0).scaled(0.5)
+    Ht = _M(np.where(inside, Hf.val, 0.0), np.where(x.val < 1.0 + 1e-3, Hf.s, 0.0), Hf.c)
+    lin = 1.0 - (0.1 - vt[0]) * 10.0
+    on_ramp = (vt[0].val > -1e-4) & (vt[0].val < 0.1 + 1e-4)
+    Vt = _M(np.clip(lin.val, 0.0, 1.0), np.where(on_ramp, lin.s, 0.0), lin.c)
+    f["terms"] = [Pt, Ht, Vt, Ut]
+    return f
+
+
+def _obs_formulas(task, f):
+    row = f["direct"] + [f["motor"], f["motor_vel"]]
+    if task == "face_direction":
+        row = row + [f["angle_obs"]]
+    elif task == "move_in_direction":
+        row = row + [f["angle_obs"]] + f["vel_target"]
+    elif task == "move_to_position":
+        row = row + f["target_body"]
+    elif task == "move_to_pose":
+        row = row + f["target_body"] + [f["angle_obs"]]
+    return row
+
+
+def _reward_formula(task, f):
+    Pt, Ht, Vt, Ut = f["terms"]
+    r = {"move_from_origin": 1.0 - Pt, "face_direction": Ht, "move_in_direction": Vt, "move_to_position": Pt, "move_to_pose": Pt * Ht}[task]
+    return r * Ut
+
+
+# the rounding counts the docstring states, as _M counts them along the formulas: [obs entries], reward, [P, H, V, U]
+_COMMON = [0, 0, 2] + [0] * 7 + [2] * 3 + [5, 2]
+ROUNDINGS = {
+    "move_from_origin": (_COMMON, 18, [16, 16, 13, 9]),
+    "face_direction": (_COMMON + [12], 17, [16, 16, 13, 9]),
+    "move_in_direction": (_COMMON + [12, 10, 10, 6], 14, [16, 16, 13, 9]),
+    "move_to_position": (_COMMON + [8, 8, 7], 17, [16, 16, 13, 9]),
+    "move_to_pose": (_COMMON + [8, 8, 7, 12], 18, [16, 16, 13, 9]),
+}
+
+
+def roundings(task):
+    f = _formulas(model.default_params(), model.qpos0()[None], np.zeros((1, 15)), np.zeros((1, 3)))
+    return [m.c for m in _obs_formulas(task, f)], _reward_formula(task, f).c, [m.c for m in f["terms"]]
+
+
+def bounds(P, task, q, v, t):
+    """dict(obs [N, D], reward [N], terms [N, 4], h [N]): the bound of every compared value on these states, and hypot(R00, R10)"""
+    f = _formulas(P, q, v, t)
+    return dict(obs=np.stack([np.broadcast_to(m.bound(), f["h"].shape) for m in _obs_formulas(task, f)], axis=1), reward=_reward_formula(task, f).bound(),
+                terms=np.stack([m.bound() for m in f["terms"]], axis=1), h=f["h"])
+
+
+def reward_bound(P, task, q, v, t):
+    return _reward_formula(task, _formulas(P, q, v, t)).bound()
+
+
+def reference(P, task, q, v, t):
+    """the oracle on these states: obs [N, D], reward [N], terms [N, 4] (P, H, V, U)"""
+    from oracle import oracle as O
+    P = np.asarray(P, dtype=np.float64)
+    Pi = (lambda i: P[i]) if P.ndim == 2 else (lambda i: P)
+    n = len(q)
+    obs = np.stack([O.observation(Pi(i), task, q[i], v[i], t[i]) for i in range(n)])
+    rew = np.array([O.reward(Pi(i), task, q[i], v[i], t[i]) for i in range(n)])
+    tm = [O.reward_terms(Pi(i), q[i], v[i], t[i]) for i in range(n)]
+    return obs, rew, np.array([[d["P"], d["H"], d["V"], d["U"]] for d in tm])
+
+
+def obs_error(task, got, ref):
+    """|got - ref| per entry, circular on the normalised angle entries"""
+    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
+    for j in ANGLE_ENTRIES[task]:
+        err[:, j] = np.minimum(err[:, j], 2.0 - err[:, j])
+    return err
+
+
+def assert_cap(b, near_vertical):
+    """the condition that keeps the bound from being vacuous (module docstring)"""
+    cap = np.where(near_vertical, STRICT_ABS / b["h"], STRICT_ABS)
+    worst = np.maximum(np.maximum(b["obs"].max(axis=1), b["terms"].max(axis=1)), b["reward"])
+    bad = np.nonzero(worst > cap)[0]
+    assert bad.size == 0, "the bound exceeds its cap on states %r: %r against %r" % (bad[:10], worst[bad[:10]], cap[bad[:10]])
+
+
+def compare(task, P, q, v, t, obs, reward, terms, families, near_vertical, what, check_cap=True):
+    """Asserts every observation entry, the reward and the four terms of every state inside the bound around the oracle of (q, v, t), the
+    cap on the bound itself, and prints max err / bound per family.  Returns {family: ratio}."""
+    ref_o, ref_r, ref_t = reference(P, task, q, v, t)
+    b = bounds(P, task, q, v, t)
+    if check_cap:
+        assert_cap(b, near_vertical)
+    eo, er, et = obs_error(task, obs, ref_o), np.abs(np.asarray(reward, dtype=np.float64) - ref_r), np.abs(np.asarray(terms, dtype=np.float64) - ref_t)
+    tiny = 1e-300
+    ratio = np.maximum(np.maximum((eo / (b["obs"] + tiny)).max(axis=1), (et / (b["terms"] + tiny)).max(axis=1)), er / (b["reward"] + tiny))
+    out = {}
+    for fam in sorted(set(families)):
+        sel = np.asarray(families) == fam
+        out[fam] = float(ratio[sel].max())
+    print("%s, %s: max err / bound per family: %s" % (what, task, ", ".join("%s %.3f" % kv for kv in out.items())))
+    for name, e, bb in (("observation", eo, b["obs"]), ("terms", et, b["terms"]), ("reward", er[:, None], b["reward"][:, None])):
+        bad = np.argwhere(e > bb)
+        assert bad.size == 0, "%s, %s: %s outside the bound at (state, entry) %r (families %r): err %r bound %r" % (
+            what, task, name, bad[:8].tolist(), [families[i] for i in bad[:8, 0]], e[tuple(bad[:8].T)], bb[tuple(bad[:8].T)])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- seam states
+def _f32(x):
+    return np.asarray(x, dtype=np.float32).astype(np.float64)
+
+
+def _ulps(x, k):
+    """the fp32 number k ulps from fp32(x)"""
+    x = np.float32(x)
+    step = np.float32(np.inf if k > 0 else -np.inf)
+    for _ in range(abs(int(k))) if abs(k) <= 64 else ():
+        x = np.nextafter(x, step)
+    if abs(k) > 64:
+        x = np.float32(x + np.float32(k) * np.spacing(np.abs(x) if x != 0 else np.float32(1e-45)))
+    return float(x)
+
+
+def _quat_mul(a, b):
+    w1, x1, y1, z1 = a
+    w2, x2, y2, z2 = b
+    return np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
+
+
+def _qz(th):
+    return np.array([np.cos(th / 2), 0.0, 0.0, np.sin(th / 2)])
+
+
+def _qy(th):
+    return np.array([np.cos(th / 2), 0.0, np.sin(th / 2), 0.0])
+
+
+def _qx(th):
+    return np.array([np.cos(th / 2), np.sin(th / 2), 0.0, 0.0])
+
+
+OFFSETS = (1, 2, 4, 64, 4096)
+
+
+def seam_states(P=None):
+    """(q [N,16], v [N,15], t [N,3], families [N], near_vertical [N]): states placed ON the branches of jb_task.hpp.  Every word is an fp32
+    number, so set_state() stores exactly these and get_state() returns them.  The robot's yaw is atan2(R10, R00) - pi/2: a pure-yaw quaternion
+    of angle th looks at th - pi/2, and angle_to_target = wrap(tpsi - th + pi/2)."""
+    P = model.default_params() if P is None else P
+    q0 = model.qpos0(P)
+    tz32 = float(np.float32(P[model.P_TARGETZ]))
+    rows, fams, nv = [], [], []
+
+    def add(fam, quat=(1.0, 0.0, 0.0, 0.0), p=(0.0, 0.0, None), lin=(0.0, 0.0, 0.0), w=(0.0, 0.0, 0.0), phi=0.0, phid=0.0, t=(0.0, 0.0, 0.0), near_vertical=False):
+        q, v = q0.copy(), np.zeros(15)
+        q[0], q[1], q[2] = p[0], p[1], q0[2] if p[2] is None else p[2]
+        q[3:7] = quat
+        q[15] = phi
+        v[0:3], v[3:6], v[14] = lin, w, phid
+        rows.append((_f32(q[:15]).tolist() + [q[15]], _f32(v), _f32(t)))
+        fams.append(fam); nv.append(near_vertical)
+
+    # ---- heading: angle_to_target at 0, +-pi/2, +-pi; exactly, and +-{1, 2, 4, 64, 4096} ulp of the yaw quaternion and of tpsi
+    s = float(np.float32(np.sqrt(0.5)))
+    moving = dict(lin=(0.05, 0.02, 0.0))                     # (so that the velocity in the target frame goes through the same tpsi)
+    for quat, tp in (((s, 0, 0, s), 0.0), ((1, 0, 0, 0), 0.0), ((0, 0, 0, 1), 0.0), ((s, 0, 0, -s), 0.0), ((s, 0, 0, s), float(np.float32(PI)))):
+        add("heading", quat, t=(0, 0, tp), **moving)           # a = 0, pi/2, -pi/2, pi exactly; and pi again through the target
+    tps = [kk * PI / 2 for kk in range(-4, 9)] + [kk * PI for kk in range(-2, 5)] + [_ulps(2 * PI, -1), -1.234, 0.77, 3.9, 7.1, 11.0]
+    for i, tp in enumerate(tps):
+        tp = float(np.float32(tp))
+        for a in (0.0, PI / 2, -PI / 2, PI, -PI):
+            th = tp + PI / 2 - a
+            quat = _f32(_qz(th))
+            add("heading", quat, t=(0, 0, tp), **moving)
+            for k in OFFSETS:
+                for sg in (1, -1):
+                    qq = quat.copy()
+                    j = 3 if abs(qq[3]) < abs(qq[0]) else 0        # the smaller of the two words: the one the angle is sensitive to
+                    qq[j] = _ulps(qq[j], sg * k)
+                    add("heading", qq, t=(0, 0, tp), **moving)
+                    add("heading", quat, t=(0, 0, _ulps(tp, sg * k)), **moving)
+    # ---- motor angle: phi + pi/2 on both sides of +-pi, with 0, +-1 and +-240 whole turns
+    for turns in (0, 1, -1, 240, -240):
+        for base in (PI / 2, -3 * PI / 2 + 2 * PI, -PI / 2, 0.0):
+            for k in (0,) + OFFSETS + tuple(-o for o in OFFSETS):
+                add("motor", phi=_ulps(base, k) + 2 * PI * turns, phid=150.0 if turns >= 0 else -150.0)
+    # ---- position: d == 0 (the parameter the kernel uses: target_z as fp32 against pz), one ulp, a log grid up to 0.5 m; far from the origin
+    add("position", p=(0, 0, tz32))
+    add("position", p=(0.125, -0.0625, tz32), t=(0.125, -0.0625, 0))
+    add("position", p=(0, 0, _ulps(tz32, 1)))
+    add("position", p=(0, 0, tz32), t=(1e-45, 0, 0))
+    add("position", p=(0.125, 0, tz32), t=(_ulps(0.125, 1), 0, 0))
+    for d in np.geomspace(1e-7, 0.5, 40):
+        for i, dirn in enumerate(((1, 0), (0, 1), (-0.6, 0.8), (0.7071, -0.7071))):
+            add("position", p=(0, 0, tz32 if i % 2 else None), t=(d * dirn[0], d * dirn[1], 0))
+    # (|p| up to 2 m, the range of the observation's own normalisation, with the target nearby: t - p cancels.  The distances are the ones the
+    # cap admits there: where the position term is steep - 2 to 60 mm - two ulps of a 2 m coordinate already move it by more than 1e-5)
+    for r, ds in ((0.0625, (1e-6, 1e-3, 0.01, 0.03, 0.05, 0.1)), (0.25, (1e-6, 1e-3, 0.07, 0.1)), (0.5, (1e-6, 1e-3, 0.07, 0.1, 0.2)), (1.0, (1e-6, 5e-4, 0.08, 0.1, 0.2)), (2.0, (1e-6, 3e-4, 0.09, 0.12, 0.3))):
+        for sx, sy in ((1, 0), (0, -1), (1, 1), (-1, 1)):
+            for d in ds:
+                px, py = sx * r, sy * r * 0.75
+                add("position_far", p=(px, py, tz32), t=(px + d * 0.6, py - d * 0.8, 0))
+    # ---- upright: Rzz == 1 and next to it, tilts on a log grid from 1e-4 rad to pi, upside down
+    for th in (0.0, 0.3, 1.0, PI / 2, 2.5, PI):
+        quat = _f32(_qz(th))
+        add("upright", quat)
+        for k in (1, 2, -1, -2):
+            qq = quat.copy(); qq[0] = _ulps(qq[0], k)
+            add("upright", qq)
+    for tilt in list(np.geomspace(1e-4, PI, 40)) + [PI]:
+        add("upright", _qx(tilt))
+        add("upright", _quat_mul(_qx(tilt), _qz(0.4)))
+    add("upright", (0, 1, 0, 0))
+    add("upright", (0, 0, 1, 0))
+    # ---- velocity: forward speed in the target frame at 0 and 0.1 and a few ulp either side, negative, 1 m/s; spin up to 35 rad/s
+    for base in (0.0, 0.1):
+        for k in (0, 1, 2, 4, -1, -2, -4):
+            vx = _ulps(base, k) if base else k * float(np.float32(1e-45))
+            add("velocity", lin=(vx, 0.03, -0.01))
+    for vx in (-1.0, -0.05, -1e-6, 1e-6, 0.03, 0.05, 0.0999, 0.1001, 0.5, 1.0):
+        add("velocity", lin=(vx, 0.02, 0.0))
+        add("velocity", (s, 0, 0, s), lin=(0.0, vx, 0.0), t=(0, 0, float(np.float32(PI / 2))))
+    # (the tilted robot looks along its target, where the heading term is flat; about several axes at once the sensor's own S - 10 |R| |w| |c0|
+    # on the ramp of the velocity term - passes the cap from 10 rad/s on, so those spins stop at 5)
+    for wz in (1.0, 10.0, 35.0, -35.0):
+        for w in ((wz, 0, 0), (0, wz, 0), (0, 0, wz)) + (((wz, -wz, 0.5 * wz),) if wz == 1.0 else ((5.0, -5.0, 2.5),)):
+            add("velocity", lin=(0.04, 0.0, 0.0), w=w)
+            if abs(wz) <= 10.0:          # (|w| |c0| = 0.39 m/s at 35 rad/s: on the ramp only the upright robot stays under the cap there)
+                add("velocity", _quat_mul(_qz(1.1), _qx(0.3)), lin=(0.0, 0.0, 0.0), w=w, t=(0, 0, 1.1 - PI / 2))
+    # ---- near-vertical: pitch so that hypot(R00, R10) runs from 1 down to 1e-3 (never zero: the heading is undefined there)
+    for hh in np.geomspace(1.0, 1e-3, 25):
+        for th in (0.0, 0.9, -2.2):
+            for sg in (1, -1):
+                add("near_vertical", _quat_mul(_qz(th), _qy(sg * np.arccos(hh))), t=(0.03, -0.02, 0.5), lin=(0.02, 0.01, 0.0), near_vertical=True)
+    q = np.array([r[0] for r in rows]); v = np.array([r[1] for r in rows]); t = np.array([r[2] for r in rows])
+    return q, v, t, fams, np.array(nv)
+
+
+# ---------------------------------------------------------------------------------------------------------------- policy seams
+NON_DEFAULT_POLICY = dict(kick_angle=0.6, speed=0.45, angle_threshold=0.2)
+
+
+def policy_rows(task, kick_angle=hp.KICK_ANGLE, speed=hp.SPEED, angle_threshold=hp.ANGLE_THRESHOLD):
+    """(obs [N, D] float32, keep [N]): observation rows that walk the variables of heuristic_policy across its thresholds on a grid of
+    +-{3, 4, 8, 64} ulp of each threshold (as fp32 holds it; float(pi/4) != pi/4), so that no directly read variable is within 2 ulp of one;
+    +-{5, 8, 64} for the angle that goes through atan2f.  keep: False on the rows whose atan2 angle is within 4 ulp of a threshold."""
+    D = model.OBS_DIM[task]
+    grid = (3, 4, 8, 64, -3, -4, -8, -64)
+    rows, keep = [], []
+
+    def around(thr):
+        return [_ulps(thr, k) for k in grid]
+
+    def add(ma=0.1, mv=1.0, extra=(), ok=True):
+        r = np.zeros(D, dtype=np.float32)
+        r[3] = 1.0; r[13] = ma; r[14] = mv
+        r[15:15 + len(extra)] = extra
+        rows.append(r); keep.append(ok)
+
+    def motor_sweep(extra, off):
+        for sg in (1, -1):
+            for ma in around(off + sg * kick_angle):
+                for mv in (0.5, -0.5):
+                    add(ma, mv, extra)
+        for mv in (0.0, 1e-45, -1e-45, 1e-6, -1e-6):
+            add(off + 0.1, mv, extra)
+
+    def atan_args(ang):
+        """(dx, dy) in fp32 with atan2(dx, -dy) as near ang as a few radii allow, and whether that angle is farther than 4 ulp from every threshold"""
+        best = None
+        for j in range(64):
+            r = 0.05 * (1 + j / 64.0)
+            dx, dy = np.float32(r * np.sin(ang)), np.float32(-r * np.cos(ang))
+            a = np.arctan2(np.float64(dx), -np.float64(dy))
+            if best is None or abs(a - ang) < best[0]:
+                best = (abs(a - ang), dx, dy, a)
+        _, dx, dy, a = best
+        thr = [sg * x for sg in (1, -1) for x in (PI / 4, PI, angle_threshold, PI / 2 - angle_threshold, PI / 2 + angle_threshold)]
+        ok = all(abs(a - x) > 4 * np.spacing(np.float32(abs(x))) for x in thr)
+        return (dx, dy), bool(ok)
+
+    def around_atan(thr):
+        """the grid for the angle that goes through atan2f: 3 and 4 ulp lie inside the zone that is left out, so it starts at 5"""
+        return [_ulps(thr, k) for k in (5, 8, 64, -5, -8, -64)]
+
+    if task == "move_from_origin":
+        motor_sweep((), 0.0)
+    elif task == "face_direction":
+        for sg in (1, -1):
+            for a in around(sg * PI / 3) + [0.0, sg * 0.5, sg * 2.0]:
+                add(extra=(a,))
+    elif task in ("move_in_direction", "move_to_position"):
+        angles = []
+        for sg in (1, -1):
+            for thr in (PI / 4, PI, angle_threshold, PI / 2 - angle_threshold, PI / 2 + angle_threshold, PI / 3):
+                angles += around(sg * thr) if task == "move_in_direction" else around_atan(sg * thr)
+        for ang in angles + [0.0, 0.1, -0.1, 1.0, -1.0, 2.5, -2.5]:
+            if task == "move_in_direction":
+                add(extra=(ang,))
+            else:
+                e, ok = atan_args(ang)
+                add(extra=e, ok=ok)
+        for off, ang in ((0.0, 0.05), (PI / 2, PI / 2 + 0.05), (-PI / 2, -PI / 2 - 0.05)):
+            extra = (ang,) if task == "move_in_direction" else atan_args(ang)[0]
+            motor_sweep(extra, off)
+    else:
+        for sg in (1, -1):
+            for ang in around_atan(sg * angle_threshold) + [sg * 1.0, sg * 3.0]:
+                e, ok = atan_args(ang)
+                add(extra=e + (0.0, 0.3), ok=ok)
+        for dist in around(0.01) + [0.0, 0.005, 0.02]:
+            for heading in (0.2, -0.2, 2.0):
+                add(extra=(0.0, -dist, 0.0, heading))
+        for sg in (1, -1):
+            for a in around(sg * PI / 3):
+                add(extra=(0.0, -0.001, 0.0, a))
+        motor_sweep((0.0, -0.05, 0.0, 0.0), 0.0)
+    return np.stack(rows), np.array(keep)
+
+
+def policy_reference(task, obs, **kw):
+    return hp.policy_batch(task, np.asarray(obs, dtype=np.float32).astype(np.float64), **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the source on the host
+def host_task_layer(lib, P, task, q, v, t, use_float, policy=None):
+    """tests/host_harness.cpp jbh_task_layer: obs [N, D], reward [N], terms [N, 4], action [N] of jb_task.hpp compiled for the host"""
+    dp = C.POINTER(C.c_double)
+    lib.jbh_task_layer.argtypes = [dp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, dp]
+    n = len(q)
+    arr = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    P, q, v, t = arr(P), arr(q), arr(v), arr(t)
+    out = np.zeros((n, 25))
+    pp = None if policy is None else arr([policy["kick_angle"], policy["speed"], policy["angle_threshold"]])
+    rc = lib.jbh_task_layer(P.ctypes.data_as(dp), model.TASKS.index(task), n, q.ctypes.data_as(dp), v.ctypes.data_as(dp), t.ctypes.data_as(dp),
+                            None if pp is None else pp.ctypes.data_as(dp), int(use_float), out.ctypes.data_as(dp))
+    assert rc == 0, rc
+    return out[:, :model.OBS_DIM[task]], out[:, 19], out[:, 20:24], out[:, 24]

@@ -177,18 +177,38 @@ def assert_protocol(r, well_bad, worst_well=None, near_cap=None, deep_share_min=
     assert r["worst_ill"] < ILL_ERROR_CAP and r["cascade_bad"] == 0, msg
     assert r["ill_frac"] <= (near_switch_cap(r["env_steps"]) if near_cap is None else near_cap), msg
     assert r["cap"] == 0, msg
+    assert_rewards(r)
     if deep_share_min is not None:
         assert r["deep_steps"] >= deep_share_min * r["env_steps"], msg          # the class really is exercised
+
+
+# Rewards.  The reward is a CONTINUOUS function of the state - no contact switch is involved -, so it is held on EVERY env-step, the near-switch
+# class included: against oracle.reward of the GPU's OWN post-step state, inside the derived bound of tests/task_reference.py (its rounding
+# counts are stated there); `reward_bad` counts the env-steps outside it and must be zero.  Next to it the reward the kernel returned against the
+# ORACLE'S step (`worst_reward_held`, over the env-steps that are not near a switch: it carries the step's own fp32 error through the reward's
+# slope) is capped by a measurement against the oracle: the worst over the full tools/parity_sweep.py run, all four kernels
+# (profiles/r09_parity_sweep.txt: REWARD_HELD_MEASURED), times two - seeds sample the tail, the convention of DEEP_ERROR_CAP.
+REWARD_HELD_MEASURED = 7.759e-6      # the tipped regime of the ordinary kernel; every other line of the record is below 2.5e-6.  reward_bad is 0 on all 51 lines
+REWARD_HELD_CAP = 2 * REWARD_HELD_MEASURED
+
+
+def assert_rewards(r):
+    msg = protocol_message(r)
+    assert r["reward_bad"] == 0, msg
+    assert r["worst_reward_held"] <= REWARD_HELD_CAP, msg
 
 
 class ParityTally:
     """The protocol's counters over a run of env-steps, whoever drives the envs (_teacher_forced below; the tests that step envs with
     device-generated models themselves).  add() takes one compared control step - the oracle env just stepped, the GPU's and the oracle's
-    observations and rewards - and returns the env-steps of the near-switch class that left the tolerance (those the cascade check follows);
-    cascade() takes the GPU's NEXT step of such envs from its own state against the oracle's from that same state; result() the figures."""
+    observations and rewards, and the GPU's post-step state (q, v, target) of the compared envs - and returns the env-steps of the near-switch
+    class that left the tolerance (those the cascade check follows); cascade() takes the GPU's NEXT step of such envs from its own state
+    against the oracle's from that same state; result() the figures.  task, P: what the rewards are the rewards of (P [NPARAM] or [n, NPARAM])."""
 
-    def __init__(self, n, contacts=True):
+    def __init__(self, n, task, P, contacts=True):
         self.n, self.contacts, self.steps = n, contacts, 0
+        self.task, self.P = task, np.asarray(P, dtype=np.float64)
+        self.reward_bad, self.worst_reward_own, self.worst_reward_ratio = 0, 0.0, 0.0
         self.tot = self.ok = self.okr = self.big = 0
         self.well_tot = self.well_ok = self.well_big = self.ill_steps = self.ill_bad_steps = self.strict_bad = self.cascade_checked = self.cascade_bad = 0
         self.deep_steps = self.deep_bad = self.deep_strict_bad = self.far_off = 0
@@ -196,8 +216,18 @@ class ParityTally:
         self.worst_clamped = self.worst_deep_converged = 0.0
         self.worst = self.worst_well = self.worst_ill = self.worst_deep = self.flip_margin_max = self.worst_reward_held = 0.0
 
-    def add(self, o, og, oo, rg, ro):
+    def add(self, o, og, oo, rg, ro, gstate):
+        from oracle import oracle as O
+        from tests import task_reference as tr
         well, deep, near = classify(o, self.contacts)
+        qg, vg, tg = gstate
+        Pi = (lambda i: self.P[i]) if self.P.ndim == 2 else (lambda i: self.P)
+        own = np.abs(rg.astype(np.float64) - np.array([O.reward(Pi(i), self.task, qg[i], vg[i], tg[i]) for i in range(self.n)]))
+        rb = tr.reward_bound(self.P, self.task, qg, vg, tg)
+        self.reward_bad += int((own > rb).sum())          # (a non-finite reward counts: the comparison is False only inside the bound)
+        self.reward_bad += int((~np.isfinite(own)).sum())
+        self.worst_reward_own = max(self.worst_reward_own, float(own.max()))
+        self.worst_reward_ratio = max(self.worst_reward_ratio, float((own / rb).max()))
         og = og.astype(np.float64)
         w = _within(og, oo)
         err = np.abs(og - oo)
@@ -250,7 +280,8 @@ class ParityTally:
                     strict_bad=int(self.strict_bad), worst_ill=float(self.worst_ill), flip_margin_max=self.flip_margin_max, cascade_checked=int(self.cascade_checked), cascade_bad=int(self.cascade_bad),
                     env_steps=env_steps, deep_steps=int(self.deep_steps), deep_bad=int(self.deep_bad), deep_strict_bad=int(self.deep_strict_bad), worst_deep=float(self.worst_deep),
                     clamped_steps=int(self.clamped_steps), clamped_strict_bad=int(self.clamped_strict_bad), worst_clamped=self.worst_clamped, worst_deep_converged=self.worst_deep_converged,
-                    unconverged_well=int(self.unconverged_well), far_off=int(self.far_off), worst_reward_held=self.worst_reward_held, **extra)
+                    unconverged_well=int(self.unconverged_well), far_off=int(self.far_off), worst_reward_held=self.worst_reward_held,
+                    reward_bad=int(self.reward_bad), worst_reward_own=self.worst_reward_own, worst_reward_ratio=self.worst_reward_ratio, **extra)
 
 
 def _teacher_forced(task, n, steps, seed, contacts=True, params=None, flat_out=False, skip=0, flags=0, actions=None, probe=None, **env_kw):
@@ -275,7 +306,7 @@ def _teacher_forced(task, n, steps, seed, contacts=True, params=None, flat_out=F
     g2 = o2 = None          # the cascade check's own pair of envs (made when first needed: their step counters must not disturb the main pair's)
     rng = np.random.default_rng(seed)
     rng2 = np.random.default_rng(seed + 1000)
-    tally = ParityTally(n, contacts)
+    tally = ParityTally(n, task, P, contacts)
 
     def draw(r):
         return np.ones(n) if flat_out else (r.uniform(-1, 1, size=n) if actions is None else actions(r, n))
@@ -290,7 +321,7 @@ def _teacher_forced(task, n, steps, seed, contacts=True, params=None, flat_out=F
         g.set_state(q, v, tg)
         og, rg, dg, _ = g.step(a)
         oo, ro, do = o.step(a, auto_reset=False)
-        ill_bad = tally.add(o, og, oo, rg, ro)
+        ill_bad = tally.add(o, og, oo, rg, ro, g.get_state())
         assert np.array_equal(dg, do.astype(bool))
         if ill_bad.any() and contacts and not dg.any():
             # a flipped contact must not cascade: from the GPU's OWN state after that step, its next step agrees with the oracle's
@@ -327,6 +358,7 @@ def test_step_teacher_forced_contacts(task):
     assert r["ill_frac"] < 0.0017, protocol_message(r)                                 # env-steps within 11 nm of a contact switch: 0.11-0.15 % (256 envs x 3 seeds; 64 envs sample that to +- 0.03 %)
     assert r["worst_ill"] < ILL_ERROR_CAP and r["cascade_bad"] == 0, protocol_message(r)      # what they may differ by, and a flip never cascades into the GPU's own next step
     assert r["frac"] >= 0.999 and r["frac_reward"] >= 0.999, protocol_message(r)      # overall, ill-conditioned env-steps included (~0.99986)
+    assert_rewards(r)                                                                  # every reward of every env-step inside its derived bound; the held ones under the measured cap
     assert r["cap"] == 0, protocol_message(r)                                          # every contact solve converged (3.2 M substeps; the line-searched second solve takes what the plain iteration leaves)
 
 
@@ -345,6 +377,7 @@ def test_step_teacher_forced_tipped_over_robots():
     # impulse: 2.5e-2; none of the seven cascades into the GPU's next step)
     assert r["ill_frac"] < 0.002 and r["frac"] >= 0.9999 and r["frac_big"] < 1e-5 and r["ill_bad_steps"] <= 20, protocol_message(r)
     assert r["worst_ill"] < ILL_ERROR_CAP and r["cascade_bad"] == 0, protocol_message(r)
+    assert_rewards(r)
     assert r["cap"] == 0, protocol_message(r)                  # every contact solve converged (256 x 300 x 50 substeps of robots lying on the floor)
 
 

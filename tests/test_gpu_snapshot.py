@@ -327,6 +327,50 @@ def test_scored_returns_match_fp64_within_the_derived_bound(case, label):
     assert np.array_equal(bits(ret_p), bits(ret)) and torch.equal(alive_p, alive)
 
 
+def test_scored_returns_stop_at_each_envs_own_first_done_step():
+    """The cases above end every env's episode on the same step.  Here the episode clocks are staggered - a masked reset part-way through the
+    lead-in - so `alive` varies over the batch and every return must stop at its OWN env's first done step; same bound as above."""
+    from jitterbug_amd.vec_env import JitterbugVecEnv
+    torch = _torch()
+    dev = torch.device("cuda", 0)
+    n, early = 37, 8
+    env = JitterbugVecEnv(n, "move_from_origin", seed=7, time_limit=0.3, envs_per_wave=2)          # (a task whose rewards are not near zero: a return that stopped late would show)
+    try:
+        D = env.obs_dim
+        g = torch.Generator(device=dev); g.manual_seed(4)
+        tape = torch.rand((PRE + K, n), generator=g, device=dev, dtype=torch.float32) * 2 - 1
+        mask = (np.arange(n) % 3 == 1).astype(np.uint8)
+        snap = torch.zeros(env.snapshot_bytes, device=dev, dtype=torch.uint8)
+        rows = torch.full((K, n, D + 2), float("nan"), device=dev)
+        ret = torch.zeros(n, device=dev); alive = torch.zeros(n, device=dev, dtype=torch.int32)
+        torch.cuda.synchronize()
+        env.reset_device()
+        env.step_many_device(early, tape[:early].contiguous().data_ptr())
+        env.synchronize()
+        env.reset(mask=mask)                                    # these envs' clocks start again, `early` steps behind the others
+        env.step_many_device(PRE - early, tape[early:PRE].contiguous().data_ptr())
+        env.snapshot_device(snap.data_ptr())
+        env.step_many_device(K, tape[PRE:].contiguous().data_ptr(), rows_ptr=rows.data_ptr())
+        env.synchronize()
+        r = rows.cpu().numpy()
+        rew, done = r[:, :, D], r[:, :, D + 1] > 0.5
+        for gamma in (1.0, 0.97):
+            env.restore_device(snap.data_ptr())
+            env.score_tapes_device(K, tape[PRE:].contiguous().data_ptr(), gamma, ret.data_ptr(), alive.data_ptr())
+            env.synchronize()
+            want, mag, want_alive = returns_fp64(rew, done, np.float32(gamma))
+            assert np.array_equal(want_alive, np.where(mask == 1, 30 - PRE + early, 30 - PRE)) and len(set(want_alive)) == 2
+            assert np.array_equal(alive.cpu().numpy(), want_alive)
+            err, bound = np.abs(ret.cpu().numpy().astype(np.float64) - want), K * 2.0 ** -23 * mag
+            print("staggered clocks, gamma %.2f: max |err| %.3e, max err / bound %.3f" % (gamma, err.max(), (err / np.maximum(bound, 1e-300)).max()))
+            assert (err <= bound).all()
+            # ... and a return that ran on to another env's done step would differ by that env's later rewards
+            late = returns_fp64(rew, np.broadcast_to(done[:, mask == 1][:, :1], done.shape), np.float32(gamma))[0]
+            assert (np.abs(late - want)[mask == 0] > 10 * bound[mask == 0]).any()
+    finally:
+        env.close()
+
+
 # ---------------------------------------------------------------------------------------------- 6. planner plumbing
 def test_mppi_planner_is_deterministic_leaves_the_plant_alone_and_applies_its_update():
     from jitterbug_amd.planning import MPPIPlanner

@@ -112,14 +112,14 @@ def test_device_compiler_matches_python_on_given_offsets_and_steps_like_the_orac
     np.testing.assert_allclose(env.reset(), o.reset(), rtol=2e-6, atol=2e-6)
     from tests.test_gpu_parity import ParityTally, assert_protocol, protocol_message
     rs, rs2 = np.random.default_rng(0), np.random.default_rng(1000)
-    tally = ParityTally(n)
+    tally = ParityTally(n, "move_to_pose", ref)
     env2 = o2 = None
     for t in range(30):
         a = rs.uniform(-1, 1, size=n)
         env.set_state(*o.get_state())
         og, rg, _, _ = env.step(a)
         oo, ro, _ = o.step(a, auto_reset=False)
-        ill_bad = tally.add(o, og, oo, rg, ro)
+        ill_bad = tally.add(o, og, oo, rg, ro, env.get_state())
         if ill_bad.any():
             # the cascade check, on a second pair of envs with the same device-compiled models: the GPU's next step from its own state
             if env2 is None:
@@ -219,7 +219,7 @@ def test_config5_shard_8192_device_models_against_the_oracle(variant):
     rew_err = np.zeros(3); worst_c = np.zeros(3)
     per_step = []
     from tests.test_gpu_parity import MARGIN_TOL, NARROW_RESID_TOL, ParityTally, assert_protocol, protocol_message
-    tally = ParityTally(64)
+    tally = ParityTally(64, task, P[idx])
     followed = np.zeros(64, bool)
     for t in range(steps):
         a = rng.uniform(-1, 1, size=n)
@@ -236,7 +236,7 @@ def test_config5_shard_8192_device_models_against_the_oracle(variant):
         # the GPU runs free, so the cascade check needs no second env: the near-switch env-steps that left the tolerance at step t are followed
         # into step t + 1, which IS the GPU's next step from its own state
         tally.cascade(followed, o, og[idx], oo)
-        followed = tally.add(o, og[idx], oo, rg[idx], ro)
+        followed = tally.add(o, og[idx], oo, rg[idx], ro, tuple(x[idx] for x in env.get_state()))
         cond = o.conditioning()
         # well and deep classes alike - but for the deep env-steps whose narrow phase stops short of its root, which the tally bounds (DEEP_ERROR_CAP)
         held = (cond["switch"] >= MARGIN_TOL) & ~(cond["deep"] & (cond["narrow_resid"] >= NARROW_RESID_TOL))
