@@ -1,6 +1,6 @@
 """The task layer (jitterbug_amd/csrc/jb_task.hpp: observation, reward, the four reward terms, the heuristic policy) against fp64, shared by
 tests/test_task_layer_host.py (the source on the host), tests/test_gpu_task_seams.py (the kernels) and the parity protocol of
-tests/test_gpu_parity.py.  Not a conftest: plain helpers.
+tests/parity_protocol.py.  Not a conftest: plain helpers.
 
 REFERENCE.  oracle.observation / oracle.reward / oracle.reward_terms in fp64, heuristic_policies.policy_batch for actions, always evaluated
 on the state AS THE DEVICE HOLDS IT (get_state() after set_state() or after a step), so that rounding the inputs is not part of a comparison.

@@ -3,13 +3,14 @@ config 1).  It is NOT a MuJoCo trace: MuJoCo cannot run here or on the GPU box (
   * CPU: the oracle still reproduces it (teacher-forced per step, 1e-9) - a change of the oracle's arithmetic is caught;
   * GPU: the HIP path, teacher-forced on the trace's states through the C ABI, matches its observations / rewards to the
     fp32 tolerance of the parity tests: every entry of every well-conditioned step within 1e-4 rel + 1e-6 abs (conditioning:
-    tests/test_gpu_parity.py MARGIN_TOL), >= 99.9 % of all entries.
+    tests/parity_protocol.py MARGIN_TOL), >= 99.9 % of all entries.
 move_from_origin is BASELINE configs[0] in full: one env, random policy, 1000 control steps."""
 import os
 import numpy as np
 import pytest
 
 from jitterbug_amd import model
+from tests.parity_protocol import MARGIN_TOL, within
 
 TRACE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_trace.npz")
 TASKS = ("move_from_origin", "move_to_pose")
@@ -45,7 +46,6 @@ def test_oracle_reproduces_trace(task):
 @pytest.mark.parametrize("task", TASKS)
 def test_hip_matches_trace(task):
     from jitterbug_amd.vec_env import JitterbugVecEnv
-    from tests.test_gpu_parity import MARGIN_TOL
     tr = _load(task)
     T, n = tr["action"].shape
     g = JitterbugVecEnv(n, task, seed=0, auto_reset=False, time_limit=float("inf"))
@@ -57,9 +57,9 @@ def test_hip_matches_trace(task):
         g.set_state(tr["qpos"][t], tr["qvel"][t], tr["target"][t])
         ob, rw, dn, _ = g.step(tr["action"][t].astype(np.float32))
         d = np.abs(ob - tr["obs"][t])
-        good = d <= 1e-4 * np.abs(tr["obs"][t]) + 1e-6
+        good = within(ob, tr["obs"][t])
         ok += good.sum(); tot += good.size
-        well = tr["margin"][t] >= MARGIN_TOL         # tests/test_gpu_parity.py: the step is not within 11 nm of a contact switch (nominal model: never deep)
+        well = tr["margin"][t] >= MARGIN_TOL         # tests/parity_protocol.py: the step is not within 11 nm of a contact switch (nominal model: never deep)
         well_bad += (~good[well]).sum(); ill += (~well).sum()
         if well.any():
             worst = max(worst, d[well].max())

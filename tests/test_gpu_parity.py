@@ -1,22 +1,21 @@
 """GPU parity tests: the HIP path (through the C ABI) against the CPU fp64 oracle on identical inputs.
 
-Tolerance (north_star: fp64 -> fp32, 1e-4 relative): an observation / reward entry PASSES when
-    |gpu - oracle| <= 1e-4 * |oracle| + 1e-6.
-Teacher-forced comparison: every control step the oracle's (qpos, qvel, target) is copied into the GPU env
-(jb_set_state keeps the fp64 height and quaternion as hi + lo fp32 words), both advance one control step (50 substeps) with the
-same action, over 1000 steps x 64 envs on all five tasks.  What is asserted, and why it is conditioned on the oracle's
-contact-switch margin, is explained above MARGIN_TOL below."""
+The tolerance lines, the classes of env-steps, what is asserted on each and the drivers are the strict parity protocol's:
+tests/parity_protocol.py.  Teacher-forced here: 1000 steps x 64 envs on all five tasks."""
 import numpy as np
 import pytest
 
 from jitterbug_amd import model
+from jitterbug_amd.vec_env import JitterbugVecEnv
+from oracle import oracle as O
+from tests.parity_inputs import thread_touching_models
+from tests.parity_protocol import (ILL_ERROR_CAP, MARGIN_TOL, assert_protocol, assert_rewards, free_running, protocol_message,
+                                   teacher_forced, within)
 
 pytestmark = pytest.mark.gpu
 
 
 def _envs(n, task, seed=0, **kw):
-    from jitterbug_amd.vec_env import JitterbugVecEnv
-    from oracle import oracle as O
     P = model.default_params()
     g = JitterbugVecEnv(n, task, seed=seed, **kw)
     okw = {}
@@ -24,10 +23,6 @@ def _envs(n, task, seed=0, **kw):
         okw["opts"] = O.default_opts(contacts=int(kw["contacts"]))
     o = O.OracleEnv(n, task, P, seed=seed, random_pose=kw.get("random_pose", True), **okw)
     return g, o
-
-
-def _within(a, b):
-    return np.abs(a - b) <= 1e-4 * np.abs(b) + 1e-6
 
 
 @pytest.mark.parametrize("task", model.TASKS)
@@ -47,7 +42,6 @@ def test_reset_matches_oracle(task):
 
 
 def test_free_fall_known_answer():
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     g = JitterbugVecEnv(8, "move_from_origin", random_pose=False, contacts=False)
     g.reset()
     g.step(np.zeros(8))
@@ -77,7 +71,6 @@ def test_state_roundtrip():
     np.testing.assert_allclose(t2, t, rtol=1e-6)
     # observation of an injected state vs the oracle's
     o.set_state(q, v, t)
-    from oracle import oracle as O
     P = model.default_params()
     og, rg = g.observe()
     for i in range(33):
@@ -86,269 +79,10 @@ def test_state_roundtrip():
     g.close()
 
 
-# Conditioning of an env-step.  Contact activation (dist < 0, MuJoCo margin 0) is the model's one discontinuity: a candidate point
-# that crosses the floor plane within the POSITION ERROR of an fp32 run at a substep boundary switches on one substep earlier or
-# later than in fp64, and the two runs then differ by one substep's contact impulse (~1e-3 in the velocities) - in ANY fp32
-# implementation, MuJoCo's own included.  The oracle reports how close each env-step came to that (jbo_stats.margin_min: the
-# smallest |distance| of any contact candidate at any of the 50 substep boundaries).  tools/flip_study.py (the kernel source on the
-# host in fp32 vs the oracle) shows every out-of-tolerance env-step has margin < 1e-8 m (10 nm; fp32 resolves the 35 mm body
-# height to 3.7 nm), and none above (on the GPU, whose compiler fuses multiply-adds its own way: 10.5 nm over 3.84 M env-steps); tools/oracle_fp32_study.py shows the same for the oracle's own algorithm compiled in fp32.  So the protocol asserts the north-star tolerance on EVERY entry of every env-step whose
-# margin is at least MARGIN_TOL, and separately bounds how many env-steps fall below it and the overall fraction.
-#
-# ONE constant for every kernel variant and every model: MARGIN_TOL is 3 ulp of the 35 mm body height in fp32 (one ulp of a number in
-# [2^-5, 2^-4) m is 2^-28 m = 3.73 nm; 3 x 3.73 nm = 11.2 nm) - the position error an fp32 run carries, not a fitted figure.
-#
-# Three classes of env-steps (OracleEnv.conditioning(): the switch margin is margins() WITHOUT the zeros a deep pair overlap forces):
-#   well         switch margin >= MARGIN_TOL, not deep                the north-star tolerance on every entry
-#   deep         switch margin >= MARGIN_TOL, deep                    a mass - leg or thread - leg pair overlaps by more than the leg's radius in some
-#                                                                     substep (the leg's axis inside the mass / the thread).  No discontinuity is involved:
-#                                                                     the contact is simulated, and held to the same strict line as the well class
-#   near-switch  switch margin < MARGIN_TOL (deep or not)             excluded from the tolerance, bounded by ILL_ERROR_CAP, cascade-checked, share capped
-# The nominal model never brings the mass or the thread near a leg: deep is never set there (asserted by the nominal tests' callers through
-# `deep_steps == 0`), so for it the classes are what they were when the protocol had two.
-MARGIN_TOL = 1.1e-8     # metres.  Round 6: tools/parity_sweep.py 256 3 on the GPU (3.84 M env-steps, profiles/r06_parity_sweep.txt) - the LARGEST margin at which an env-step left the strict tolerance is 10.5 nm; tools/flip_study.py (the packed-fp32 source on the host, 6400 env-steps): every one in [1, 10) nm, none of the 24 in [10, 30) nm
-
-
-# What the excluded env-steps may differ by: a contact that switches on one substep earlier or later than in fp64 leaves the step with one
-# substep's contact impulse more or less - for this robot (17.5 g, contact forces up to a few times its weight within 0.2 ms, a motor that
-# spins at 150 rad/s) at most a few 1e-2 in a normalised observation entry (measured worst: 2.5e-2, a tipped robot).
-ILL_ERROR_CAP = 5e-2
-
-# The deep class has a part of its own.  The mass - leg narrow phase is a FIXED-COUNT iteration (jb_sim.hpp pair_narrow = jb_oracle.c
-# pair_geometric: what the counts reach is the contact's definition).  On shallow contacts it reaches the root to round-off; with the leg's
-# axis deep inside the flat mass ellipsoid the multiplier runs into its clamp (-0.95 min s^2) and the counts stop short of the root - the
-# oracle reports the residual they leave (conditioning()["narrow_resid"]: 3.6e-9 at most on env-steps that are not deep, 0.8-1.0 where the
-# clamp holds).  Such a contact is a function of every rounding on the way: the same source in fp64 equals the oracle (1.7e-7), in fp32 it
-# is off by up to 1.5e-3 in an observation entry on 6 of 141 such env-steps (tools/flip_study.py, profiles/r07_flip_study_pair.txt), and
-# the oracle's own step from the same state rounded to fp32 already differs by up to 2.8e-5 there.
-# So: deep env-steps whose narrow phase CONVERGED (residual < NARROW_RESID_TOL) are held to the strict line like the well class; the
-# UNCONVERGED ones (`clamped_*` keys) are bounded by DEEP_ERROR_CAP - never unbounded.
-NARROW_RESID_TOL = 1e-6      # 8 ulp of 1 in fp32: the root as well as fp32 can state it
-# Measured against the oracle on the GPU, profiles/r07_parity_sweep.txt: the largest error on an unconverged deep env-step over the sweep is
-# 2.4e-3 (lines "augmented_params(256, seed=5) x 1000, seed 6", PAIR and LEAN + PAIR alike: 434 such env-steps, 47 entries outside the strict
-# tolerance; every other line of the sweep - up to 47 such env-steps each - has none outside it, worst 2.1e-6).  Twice that: seeds sample the tail.
-DEEP_ERROR_CAP = 5e-3
-
-# Share of near-switch env-steps a per-env-model run may have.  A CAP, not a measurement: the oracle alone gives 0.07-0.20 % on the inputs of
-# these tests (tests/test_pair_contact.py::test_oracle_reports_deep_overlap_and_switch_margin_separately prints them), the binomial spread
-# at 9600-19 200 env-steps is +- 0.03-0.04 %.  Runs shorter than 9600 env-steps add three binomial spreads of their own size (near_switch_cap).
-NEAR_SWITCH_CAP = 0.003
-
-
-def near_switch_cap(env_steps):
-    if env_steps >= 9600:
-        return NEAR_SWITCH_CAP
-    return NEAR_SWITCH_CAP + 3 * np.sqrt(0.0015 * (1 - 0.0015) / env_steps)          # 0.15 %: the nominal near-switch share
-
-
-def classify(o, contacts=True):
-    """(well, deep, near) masks of the oracle env's last control step - the three classes above"""
-    if not contacts:
-        return np.ones(o.n, bool), np.zeros(o.n, bool), np.zeros(o.n, bool)
-    c = o.conditioning()
-    near = c["switch"] < MARGIN_TOL
-    return ~near & ~c["deep"], ~near & c["deep"], near
-
-
-def unconverged(o, contacts=True):
-    """env-steps of the oracle env's last control step in which the mass - leg narrow phase's fixed counts stopped short of the root"""
-    return o.conditioning()["narrow_resid"] >= NARROW_RESID_TOL if contacts else np.zeros(o.n, bool)
-
-
-def protocol_message(r):
-    """what an assertion of the protocol shows when it fails: the whole result, the figure MARGIN_TOL has to cover first"""
-    return "largest switch margin of an env-step outside the strict tolerance (flip_margin_max) %.2f nm, MARGIN_TOL %.1f nm; %r" % (r["flip_margin_max"] * 1e9, MARGIN_TOL * 1e9, r)
-
-
-def assert_protocol(r, well_bad, worst_well=None, near_cap=None, deep_share_min=None):
-    """The strict parity protocol on one result of a ParityTally - every per-env-model test asserts ALL of it: on the well class the
-    north-star line counted (`well_bad` entries at most outside 1e-4 rel + 1e-6 abs, none by 1e-2; where the caller bounds it, none by
-    `worst_well`) and exact (strict_bad == 0: 1e-4 rel + 1e-5 abs on every entry); on the deep class the same exact line
-    (no entry of a deep env-step with a converged narrow phase outside it; the unconverged ones below DEEP_ERROR_CAP) and the same
-    `worst_well`; near-switch env-steps bounded in error, never cascading, capped in number
-    (NEAR_SWITCH_CAP unless the caller's own bound is tighter); every contact solve converged."""
-    msg = protocol_message(r)
-    assert r["well_bad"] <= well_bad and r["well_big"] == 0, msg
-    assert r["strict_bad"] == 0, msg
-    assert r["deep_strict_bad"] - r["clamped_strict_bad"] == 0, msg          # deep, narrow phase converged: the strict line
-    assert r["worst_clamped"] < DEEP_ERROR_CAP, msg                          # deep, narrow phase unconverged: bounded
-    if worst_well is not None:
-        assert r["worst_well"] < worst_well and r["worst_deep_converged"] < worst_well, msg
-    assert r["worst_ill"] < ILL_ERROR_CAP and r["cascade_bad"] == 0, msg
-    assert r["ill_frac"] <= (near_switch_cap(r["env_steps"]) if near_cap is None else near_cap), msg
-    assert r["cap"] == 0, msg
-    assert_rewards(r)
-    if deep_share_min is not None:
-        assert r["deep_steps"] >= deep_share_min * r["env_steps"], msg          # the class really is exercised
-
-
-# Rewards.  The reward is a CONTINUOUS function of the state - no contact switch is involved -, so it is held on EVERY env-step, the near-switch
-# class included: against oracle.reward of the GPU's OWN post-step state, inside the derived bound of tests/task_reference.py (its rounding
-# counts are stated there); `reward_bad` counts the env-steps outside it and must be zero.  Next to it the reward the kernel returned against the
-# ORACLE'S step (`worst_reward_held`, over the env-steps that are not near a switch: it carries the step's own fp32 error through the reward's
-# slope) is capped by a measurement against the oracle: the worst over the full tools/parity_sweep.py run, all four kernels
-# (profiles/r09_parity_sweep.txt: REWARD_HELD_MEASURED), times two - seeds sample the tail, the convention of DEEP_ERROR_CAP.
-REWARD_HELD_MEASURED = 7.759e-6      # the tipped regime of the ordinary kernel; every other line of the record is below 2.5e-6.  reward_bad is 0 on all 51 lines
-REWARD_HELD_CAP = 2 * REWARD_HELD_MEASURED
-
-
-def assert_rewards(r):
-    msg = protocol_message(r)
-    assert r["reward_bad"] == 0, msg
-    assert r["worst_reward_held"] <= REWARD_HELD_CAP, msg
-
-
-class ParityTally:
-    """The protocol's counters over a run of env-steps, whoever drives the envs (_teacher_forced below; the tests that step envs with
-    device-generated models themselves).  add() takes one compared control step - the oracle env just stepped, the GPU's and the oracle's
-    observations and rewards, and the GPU's post-step state (q, v, target) of the compared envs - and returns the env-steps of the near-switch
-    class that left the tolerance (those the cascade check follows); cascade() takes the GPU's NEXT step of such envs from its own state
-    against the oracle's from that same state; result() the figures.  task, P: what the rewards are the rewards of (P [NPARAM] or [n, NPARAM])."""
-
-    def __init__(self, n, task, P, contacts=True):
-        self.n, self.contacts, self.steps = n, contacts, 0
-        self.task, self.P = task, np.asarray(P, dtype=np.float64)
-        self.reward_bad, self.worst_reward_own, self.worst_reward_ratio = 0, 0.0, 0.0
-        self.tot = self.ok = self.okr = self.big = 0
-        self.well_tot = self.well_ok = self.well_big = self.ill_steps = self.ill_bad_steps = self.strict_bad = self.cascade_checked = self.cascade_bad = 0
-        self.deep_steps = self.deep_bad = self.deep_strict_bad = self.far_off = 0
-        self.clamped_steps = self.clamped_strict_bad = self.unconverged_well = 0
-        self.worst_clamped = self.worst_deep_converged = 0.0
-        self.worst = self.worst_well = self.worst_ill = self.worst_deep = self.flip_margin_max = self.worst_reward_held = 0.0
-
-    def add(self, o, og, oo, rg, ro, gstate):
-        from oracle import oracle as O
-        from tests import task_reference as tr
-        well, deep, near = classify(o, self.contacts)
-        qg, vg, tg = gstate
-        Pi = (lambda i: self.P[i]) if self.P.ndim == 2 else (lambda i: self.P)
-        own = np.abs(rg.astype(np.float64) - np.array([O.reward(Pi(i), self.task, qg[i], vg[i], tg[i]) for i in range(self.n)]))
-        rb = tr.reward_bound(self.P, self.task, qg, vg, tg)
-        self.reward_bad += int((own > rb).sum())          # (a non-finite reward counts: the comparison is False only inside the bound)
-        self.reward_bad += int((~np.isfinite(own)).sum())
-        self.worst_reward_own = max(self.worst_reward_own, float(own.max()))
-        self.worst_reward_ratio = max(self.worst_reward_ratio, float((own / rb).max()))
-        og = og.astype(np.float64)
-        w = _within(og, oo)
-        err = np.abs(og - oo)
-        self.steps += 1
-        self.ok += w.sum(); self.tot += w.size
-        self.okr += _within(rg.astype(np.float64), ro).sum()
-        self.big += (err > 1e-2).sum()
-        self.worst = max(self.worst, err.max())
-        self.well_tot += w[well].size; self.well_ok += w[well].sum(); self.well_big += (err[well] > 1e-2).sum()
-        strict = err > 1e-4 * np.abs(oo) + 1e-5
-        viol = strict.any(axis=1)              # env-steps with an entry outside the strict tolerance, whatever their class
-        self.strict_bad += int(strict[well].sum())
-        self.far_off += int((err > 1e-3 * np.abs(oo) + 1e-5).any(axis=1).sum())
-        flipped = viol & ~(deep & unconverged(o, self.contacts))          # (what leaves the tolerance in the unconverged part of the deep class is no flip: DEEP_ERROR_CAP)
-        if self.contacts and flipped.any():
-            self.flip_margin_max = max(self.flip_margin_max, float(o.conditioning()["switch"][flipped].max()))      # the LARGEST contact-switch margin at which fp32 still flipped: what MARGIN_TOL must cover
-        if well.any():
-            self.worst_well = max(self.worst_well, err[well].max())
-            self.unconverged_well += int((well & unconverged(o, self.contacts)).sum())
-        if deep.any():
-            self.deep_steps += int(deep.sum()); self.deep_bad += int((~w[deep]).sum())
-            self.deep_strict_bad += int(strict[deep].sum())
-            self.worst_deep = max(self.worst_deep, float(err[deep].max()))
-            cl = deep & unconverged(o, self.contacts)
-            self.clamped_steps += int(cl.sum()); self.clamped_strict_bad += int(strict[cl].sum())
-            if cl.any():
-                self.worst_clamped = max(self.worst_clamped, float(err[cl].max()))
-            if (deep & ~cl).any():
-                self.worst_deep_converged = max(self.worst_deep_converged, float(err[deep & ~cl].max()))
-        if (~near).any():
-            self.worst_reward_held = max(self.worst_reward_held, float(np.abs(rg.astype(np.float64) - ro)[~near].max()))
-        ill_bad = near & ~w.all(axis=1)
-        self.ill_steps += near.sum(); self.ill_bad_steps += ill_bad.sum()
-        if near.any():
-            self.worst_ill = max(self.worst_ill, err[near].max())
-        return ill_bad
-
-    def cascade(self, followed, o2, og2, oo2):
-        sel = followed & ~classify(o2, self.contacts)[2]          # (that next step is held to the strict line whether it is deep or not)
-        self.cascade_checked += int(sel.sum())
-        if sel.any():
-            og2 = og2.astype(np.float64)
-            self.cascade_bad += int((~(np.abs(og2[sel] - oo2[sel]) <= 1e-4 * np.abs(oo2[sel]) + 1e-5).all(axis=1)).sum())
-
-    def result(self, cap, **extra):
-        env_steps = self.n * self.steps
-        return dict(well_bad=int(self.well_tot - self.well_ok), frac=self.ok / self.tot, worst=self.worst, frac_reward=self.okr / env_steps, cap=float(cap), frac_big=self.big / self.tot,
-                    well_frac=self.well_ok / max(self.well_tot, 1), well_big=int(self.well_big), worst_well=self.worst_well,
-                    ill_frac=self.ill_steps / env_steps, ill_steps=int(self.ill_steps), ill_bad_steps=int(self.ill_bad_steps),
-                    strict_bad=int(self.strict_bad), worst_ill=float(self.worst_ill), flip_margin_max=self.flip_margin_max, cascade_checked=int(self.cascade_checked), cascade_bad=int(self.cascade_bad),
-                    env_steps=env_steps, deep_steps=int(self.deep_steps), deep_bad=int(self.deep_bad), deep_strict_bad=int(self.deep_strict_bad), worst_deep=float(self.worst_deep),
-                    clamped_steps=int(self.clamped_steps), clamped_strict_bad=int(self.clamped_strict_bad), worst_clamped=self.worst_clamped, worst_deep_converged=self.worst_deep_converged,
-                    unconverged_well=int(self.unconverged_well), far_off=int(self.far_off), worst_reward_held=self.worst_reward_held,
-                    reward_bad=int(self.reward_bad), worst_reward_own=self.worst_reward_own, worst_reward_ratio=self.worst_reward_ratio, **extra)
-
-
-def _teacher_forced(task, n, steps, seed, contacts=True, params=None, flat_out=False, skip=0, flags=0, actions=None, probe=None, **env_kw):
-    """Returns, next to the north-star counts (1e-4 rel + 1e-6 abs per entry): `strict_bad` - entries of well-conditioned env-steps outside
-    1e-4 rel + 1e-5 abs (fp32 cannot hold 1e-6 absolute on an entry that is a difference of O(1) terms: eps x 8 roundings; asserted to be
-    ZERO by the callers, no counting) -, `worst_ill` - the largest error on an excluded env-step (bounded by ILL_ERROR_CAP) - and the CASCADE
-    check: whenever an excluded env-step is out of tolerance, the GPU's own NEXT step from its own resulting state is held against the oracle's
-    from that same state (`cascade_checked` env-steps, `cascade_bad` of them outside the tolerance where that step is well-conditioned).
-    Every `well_*` key, `strict_bad` and `worst_well` are over the WELL class; `deep_steps` / `deep_bad` (entries outside 1e-4 rel + 1e-6 abs) /
-    `deep_strict_bad` (outside 1e-4 rel + 1e-5 abs) / `worst_deep` the same figures over the DEEP class, `clamped_*` over its env-steps with an
-    unconverged narrow phase and `worst_deep_converged` over the others (see DEEP_ERROR_CAP); `ill_*` and `worst_ill` over the
-    NEAR-SWITCH class alone (see MARGIN_TOL).  `flip_margin_max`: the largest SWITCH margin of an env-step outside the strict tolerance.
-    actions(rng, n): another action stream than uniform / flat out; probe(t, q, v, a): called with the oracle's pre-step state."""
-    from oracle import oracle as O
-    P = model.default_params() if params is None else params
-    per_env = P.ndim == 2
-    from jitterbug_amd.vec_env import JitterbugVecEnv
-    g = JitterbugVecEnv(n, task, seed=seed, auto_reset=False, contacts=contacts, params=P if per_env else None, flags=flags, **env_kw)
-    okw = dict(opts=O.default_opts(contacts=int(contacts)), per_env_model=per_env)
-    o = O.OracleEnv(n, task, P, seed=seed, **okw)
-    g.reset(), o.reset()
-    g2 = o2 = None          # the cascade check's own pair of envs (made when first needed: their step counters must not disturb the main pair's)
-    rng = np.random.default_rng(seed)
-    rng2 = np.random.default_rng(seed + 1000)
-    tally = ParityTally(n, task, P, contacts)
-
-    def draw(r):
-        return np.ones(n) if flat_out else (r.uniform(-1, 1, size=n) if actions is None else actions(r, n))
-    for t in range(-skip, steps):
-        a = draw(rng)
-        if t < 0:                                       # lead-in on the oracle alone (robots tip over), not compared
-            o.step(a, auto_reset=False)
-            continue
-        q, v, tg = o.get_state()
-        if probe is not None:
-            probe(t, q, v, a)
-        g.set_state(q, v, tg)
-        og, rg, dg, _ = g.step(a)
-        oo, ro, do = o.step(a, auto_reset=False)
-        ill_bad = tally.add(o, og, oo, rg, ro, g.get_state())
-        assert np.array_equal(dg, do.astype(bool))
-        if ill_bad.any() and contacts and not dg.any():
-            # a flipped contact must not cascade: from the GPU's OWN state after that step, its next step agrees with the oracle's
-            if g2 is None:
-                g2 = JitterbugVecEnv(n, task, seed=seed, auto_reset=False, contacts=contacts, params=P if per_env else None, flags=flags, time_limit=float("inf"), **env_kw)
-                o2 = O.OracleEnv(n, task, P, seed=seed, **okw)
-                g2.reset(), o2.reset()
-            q2, v2, t2 = g.get_state()
-            g2.set_state(q2, v2, t2); o2.set_state(q2, v2, t2)
-            a2 = draw(rng2)
-            og2 = g2.step(a2)[0]
-            oo2 = o2.step(a2, auto_reset=False)[0]
-            tally.cascade(ill_bad, o2, og2, oo2)
-    sc, ep, cap = g.counters()
-    variant = g.kernel_variant
-    g.close()
-    if g2 is not None:
-        g2.close()
-    q, _, _ = o.get_state()
-    tipped = float(((1 - 2 * (q[:, 4] ** 2 + q[:, 5] ** 2)) < 0.5).mean())
-    return tally.result(cap.sum(), tipped=tipped, kernel_variant=variant)
-
-
 @pytest.mark.parametrize("task", model.TASKS)
 def test_step_teacher_forced_contacts(task):
     """SURVEY 8(d) protocol in full: 64 envs x 1000 control steps (one whole episode), every task, teacher-forced."""
-    r = _teacher_forced(task, 64, 1000, seed=3 + model.TASKS.index(task))      # another seed per task: five different sets of trajectories
+    r = teacher_forced(task, 64, 1000, seed=3 + model.TASKS.index(task))      # another seed per task: five different sets of trajectories
     print("teacher-forced", task, r)
     assert r["deep_steps"] == 0, protocol_message(r)          # the nominal robot never has a pair overlap: two classes, as before there were three
     # well-conditioned env-steps: measured over the five seeds 0, 1, 2, 0, 0 of ~1.1 M entries each outside 1e-4 rel + 1e-6 abs, the
@@ -366,7 +100,7 @@ def test_step_teacher_forced_tipped_over_robots():
     """The same protocol where the all-geom path does the work: motor flat out for 250 steps (oracle alone), then 300 compared steps with
     about a third of the robots lying on their legs - upper-leg cylinders, knee tips and body geoms in contact, 8+ live slots per leg.
     256 envs (at 64 the unconverged solves of round 4 - 11 well-conditioned entries off by up to 1.1e-3 - did not show)."""
-    r = _teacher_forced("move_to_pose", 256, 300, seed=55, flat_out=True, skip=250)
+    r = teacher_forced("move_to_pose", 256, 300, seed=55, flat_out=True, skip=250)
     print("teacher-forced, tipped:", r)
     assert r["deep_steps"] == 0, protocol_message(r)
     assert r["tipped"] > 0.25, protocol_message(r)
@@ -385,12 +119,11 @@ def test_lean_kernel_variant_parity():
     """JB_FLAG_LEAN: the two-waves-per-SIMD variant of the step kernel (256 VGPRs, no AGPRs - profiles/r06_kernel_resources.txt; state / system / factorisation parked in LDS,
     20 KB of LDS per four-env wave) under the same protocol, and against the ordinary variant from identical states (the compiler fuses multiply-adds differently in
     the two kernels, so they agree to rounding, not bit for bit - on the host, without contraction, they are identical)."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
-    r = _teacher_forced("move_to_pose", 64, 200, seed=7, flags=2)
+    r = teacher_forced("move_to_pose", 64, 200, seed=7, flags=2)
     print("teacher-forced, lean kernel:", r)
     assert r["deep_steps"] == 0, protocol_message(r)
     assert r["well_bad"] <= 2 and r["strict_bad"] == 0 and r["well_big"] == 0 and r["frac"] >= 0.999 and r["cap"] == 0 and r["cascade_bad"] == 0, protocol_message(r)
-    r = _teacher_forced("move_to_pose", 64, 100, seed=5, flat_out=True, skip=250, flags=2)
+    r = teacher_forced("move_to_pose", 64, 100, seed=5, flat_out=True, skip=250, flags=2)
     assert r["tipped"] > 0.15 and r["well_bad"] <= 3 and r["strict_bad"] == 0 and r["worst_well"] < 2e-5 and r["frac"] >= 0.9999 and r["cap"] == 0, protocol_message(r)
     n = 1024
     a_env, b_env = JitterbugVecEnv(n, "move_to_pose", seed=6), JitterbugVecEnv(n, "move_to_pose", seed=6, flags=2)
@@ -402,7 +135,7 @@ def test_lean_kernel_variant_parity():
         b_env.set_state(*a_env.get_state())
         oa, ra, _, _ = a_env.step(act)
         ob, rb, _, _ = b_env.step(act)
-        good = np.abs(oa - ob) <= 1e-4 * np.abs(ob) + 1e-6
+        good = within(oa, ob)
         ok += good.sum(); tot += good.size
     assert ok / tot >= 0.999, ok / tot
     a_env.close(); b_env.close()
@@ -413,8 +146,6 @@ def test_lean_kernel_at_the_size_it_is_selected_for_against_the_oracle():
     oracle-checked at 64 envs (one wave per SIMD).  Here: 8192 envs of the nominal model, the product's own variant selection, two resident
     waves per SIMD, a free-running open-loop rollout of 200 control steps; a 64-env subset spread over the batch is held against the oracle every
     step from the GPU's own pre-step state (teacher-forced the other way round, like the config-5 shard test)."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
-    from oracle import oracle as O
     n, steps, task = 8192, 200, "move_from_origin"
     env = JitterbugVecEnv(n, task, seed=21, auto_reset=False, variant="auto")
     assert env.kernel_variant == "lean" and env.envs_per_wave == 4
@@ -425,19 +156,18 @@ def test_lean_kernel_at_the_size_it_is_selected_for_against_the_oracle():
     rng = np.random.default_rng(5)
     well_bad = well_tot = ill = 0
     worst_well = worst_rew = 0.0
-    for t in range(steps):
-        a = rng.uniform(-1, 1, size=n)
-        a[idx[:16]] = 1.0                       # a quarter of the compared robots flat out: some of them tip over (all-geom path)
-        q, v, tg = env.get_state()
-        og, rg, dg, _ = env.step(a)
-        o.set_state(q[idx], v[idx], tg[idx])
-        oo, ro, do = o.step(a[idx], auto_reset=False)
+
+    flat_out = np.isin(np.arange(n), idx[:16])          # a quarter of the compared robots flat out: some of them tip over (all-geom path)
+
+    def compare(t, pre, og, rg, oo, ro, o):
+        nonlocal well_bad, well_tot, ill, worst_well, worst_rew
         well = o.margins() >= MARGIN_TOL
-        err = np.abs(og[idx].astype(np.float64) - oo)
-        w = err <= 1e-4 * np.abs(oo) + 1e-6
+        err = np.abs(og - oo)          # (fp32 - fp64: taken in fp64)
+        w = within(og, oo)
         well_bad += (~w[well]).sum(); well_tot += w[well].size; ill += (~well).sum()
         if well.any():
-            worst_well = max(worst_well, err[well].max()); worst_rew = max(worst_rew, np.abs(rg[idx] - ro)[well].max())
+            worst_well = max(worst_well, err[well].max()); worst_rew = max(worst_rew, np.abs(rg - ro)[well].max())
+    free_running(env, o, idx, steps, lambda t: np.where(flat_out, 1.0, rng.uniform(-1, 1, size=n)), hook=compare)
     q, v, _ = env.get_state()
     tipped = float(((1 - 2 * (q[idx, 4] ** 2 + q[idx, 5] ** 2)) < 0.5).mean())
     print("LEAN at 8192 envs vs the oracle: well-conditioned entries outside the tolerance %d of %d (worst %.1e, worst reward error %.1e), ill-conditioned env-steps %d of %d, tipped %.2f"
@@ -453,7 +183,6 @@ def test_lean_variant_at_two_waves_per_simd_is_split_invariant_and_physical():
     """The LEAN variant where it pays (>= 8192 envs on a GPU: 2048+ four-env waves, two resident per SIMD, 20 KB of LDS each): 16 384 envs,
     results bit-identical for any split into LEAN shards (the variant is a per-handle choice - JB_FLAG_LEAN - because its arithmetic is
     rounded differently from the ordinary kernel's: every shard of a batch must use the same one), deterministic, physical."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n = 16384
     rng = np.random.default_rng(1)
     acts = rng.uniform(-1, 1, size=(8, n)).astype(np.float32)
@@ -484,7 +213,7 @@ def test_lean_variant_at_two_waves_per_simd_is_split_invariant_and_physical():
 
 def test_step_teacher_forced_contacts_off():
     """BASELINE configs[1] (contacts off: free-body dynamics): no discontinuity, every entry within tolerance over a whole episode."""
-    r = _teacher_forced("move_from_origin", 64, 1000, seed=4, contacts=False)
+    r = teacher_forced("move_from_origin", 64, 1000, seed=4, contacts=False)
     print("teacher-forced contacts off:", r)
     assert r["frac"] == 1.0 and r["frac_big"] == 0.0, r          # (10 s of free fall: |z| reaches 490 m, so only the relative tolerance is meaningful)
 
@@ -495,13 +224,10 @@ def test_all_geoms_contact_parity(variant):
     motor-body geoms) through the complete-collision path of every kernel variant - up to fifteen contacts per robot, i.e. also the
     candidates beyond the row cache (LEAN: in global memory).  The PAIR variants run one model per env, robots whose thread rubs a front leg
     (tests/test_thread_contact.py) next to the nominal one, so the geom-geom contacts are live among the floor contacts."""
-    from oracle import oracle as O
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n = 256
     rng = np.random.default_rng(5)
     if variant in ("pair", "lean_pair"):
-        from tests.test_thread_contact import _touching_models
-        models = [m[0] for m in _touching_models(6, seed=11)] + [model.default_params()]
+        models = [m[0] for m in thread_touching_models(6, seed=11)] + [model.default_params()]
         P = np.stack([models[i % len(models)] for i in range(n)])
         Pi = lambda i: P[i]
     else:
@@ -571,14 +297,13 @@ def test_every_launch_row_against_the_oracle(variant, epw):
     CPU with OracleEnv.conditioning() for n = 3, 5, 9, 17 nominal and n = 9 augmented at seed 3: the smallest switch margin is 1.1e-7 m against
     MARGIN_TOL 1.1e-8), so every env-step is in the well class and is held to the suite's well-class line, 2e-5."""
     from jitterbug_amd import _lib, augmented_jitterbug as aj
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n = 2 * epw + 1
     flags = {"ordinary": 0, "pair": _lib.FLAG_PAIR, "lean": _lib.FLAG_LEAN, "lean_pair": _lib.FLAG_LEAN}[variant]
     params = aj.augmented_params(n, seed=3) if variant == "lean_pair" else None
     g = JitterbugVecEnv(n, "move_to_pose", seed=3, params=params, flags=flags, envs_per_wave=epw)
     assert g.kernel_variant == variant and g.envs_per_wave == epw
     g.close()
-    r = _teacher_forced("move_to_pose", n, 8, seed=3, params=params, flags=flags, envs_per_wave=epw)
+    r = teacher_forced("move_to_pose", n, 8, seed=3, params=params, flags=flags, envs_per_wave=epw)
     print("launch row %s at %d envs per wave:" % (variant, epw), r)
     assert r["kernel_variant"] == variant, r
     assert_protocol(r, well_bad=0, worst_well=2e-5, near_cap=0)
@@ -588,7 +313,6 @@ def test_every_launch_row_against_the_oracle(variant, epw):
 def test_auto_reset_and_episode_streams():
     g, o = _envs(50, "move_to_position", seed=9, time_limit=0.05)      # 5 control steps per episode
     o2 = None
-    from oracle import oracle as O
     o = O.OracleEnv(50, "move_to_position", model.default_params(), seed=9, step_limit=5)
     g.reset(), o.reset()
     rng = np.random.default_rng(1)
@@ -609,7 +333,6 @@ def test_auto_reset_and_episode_streams():
 def test_sharding_invariance_and_determinism_full_size():
     """BASELINE size (N=4096): results are bit-identical run to run, and do not depend on how the batch is
     split into shards (env_offset), which is what makes the multi-GPU path a pure partition."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n = 4096
     rng = np.random.default_rng(0)
     acts = rng.uniform(-1, 1, size=(6, n)).astype(np.float32)
@@ -644,7 +367,7 @@ def test_per_env_randomised_models():
     from jitterbug_amd import augmented_jitterbug as aj
     n = 256
     P = aj.augmented_params(n, seed=5)
-    r = _teacher_forced("move_to_pose", n, 200, seed=6, params=P)
+    r = teacher_forced("move_to_pose", n, 200, seed=6, params=P)
     print("per-env models:", r)
     assert r["kernel_variant"] == "pair", r
     # the whole protocol (well_bad 0: as before, when this test asked well_frac == 1.0); 10 of the 256 robots reach a deep overlap, 0.78 % of the env-steps
@@ -657,8 +380,6 @@ def test_edge_cases_batch_sizes_and_layouts():
     """Odd batch sizes (tail quads / partially filled waves), every envs-per-wave instantiation, masked reset, partial
     set_state, other substep counts, infinite time limit, argument errors."""
     from jitterbug_amd import _lib
-    from jitterbug_amd.vec_env import JitterbugVecEnv
-    from oracle import oracle as O
     P = model.default_params()
     rng = np.random.default_rng(0)
     ref = {}
@@ -730,8 +451,6 @@ def test_open_loop_statistics_match_oracle():
     """Open-loop rollouts are chaotic (contact activations), so beyond one control step GPU and oracle agree in DISTRIBUTION:
     same reset streams, same action streams, 512 envs x 250 steps; compared: episode return, displacement from the origin,
     height, uprightness (SURVEY.md §8d 'open-loop statistical agreement')."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
-    from oracle import oracle as O
     n, steps = 512, 250
     P = model.default_params()
     g = JitterbugVecEnv(n, "move_from_origin", seed=12)
@@ -771,7 +490,6 @@ def test_full_episode_properties_at_config4_size():
     """BASELINE configs[3] shape on one GPU (move_to_pose, 32768 envs): a whole 1000-step episode plus the auto-reset, checked
     through size-independent properties - finite, unit quaternions, rewards in [0, 1], `done` exactly at the step limit,
     targets re-drawn in their range at the reset, and the result does not depend on how the batch is split."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n, task = 32768, "move_to_pose"
     D = model.OBS_DIM[task]
     env = JitterbugVecEnv(n, task, seed=21)
@@ -815,7 +533,6 @@ def test_full_episode_properties_at_config4_size():
 def test_packed_rows_equal_separate_outputs():
     """jb_step_rows_device writes [obs | reward | done] rows from the step kernel itself: bit-identical to jb_step_device."""
     import torch
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n, task = 1031, "move_to_pose"
     D = model.OBS_DIM[task]
     a_env = JitterbugVecEnv(n, task, seed=3, time_limit=0.07)         # 7 control steps per episode
@@ -842,7 +559,6 @@ def test_random_policy_returns_in_the_reference_figures_bands():
     ~310-330 for move_in_direction and ~200-230 for face_direction.  A uniform-random policy on this simulator must land in
     generous bands around those values (it does: 863 / 318 / 219, profiles/r01_policy_returns.txt) - a coarse statistical pin
     of locomotion speed, vibration amplitude and turning, not a parity claim."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     bands = {"move_from_origin": (650, 950), "move_in_direction": (220, 420), "face_direction": (100, 400)}
     n = 256
     for task, (lo, hi) in bands.items():
@@ -863,7 +579,6 @@ def test_no_uninitialised_scratch_is_read():
     """Regression (rank-one Newton pass, round 1): a lane without a flipped contact read a row-cache entry nobody had written
     in that substep; the result depended on what the previous kernel had left in LDS.  LDS is poisoned with NaNs before every
     launch: results must stay finite, every contact solve must converge, and the run must equal an un-poisoned one bit for bit."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n = 4096
     rng = np.random.default_rng(0)
     acts = rng.uniform(-1, 1, size=(120, n)).astype(np.float32)
@@ -887,7 +602,6 @@ def test_no_uninitialised_scratch_is_read():
 
 def test_all_geom_regime_stays_finite_with_poisoned_scratch():
     """Same check where most waves take the all-geom path (motor flat out: about half the robots tip over)."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n = 2048
     env = JitterbugVecEnv(n, "move_to_pose", seed=4)
     env.reset()
@@ -908,7 +622,6 @@ def test_all_geom_regime_stays_finite_with_poisoned_scratch():
 
 def test_non_finite_state_is_flagged_in_the_failure_counter():
     """A control step that ends non-finite adds 1000 to the env's failure counter (jb_get_counters), and only that env's."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     env = JitterbugVecEnv(9, "move_from_origin", seed=1)
     env.reset()
     env.step(np.zeros(9, dtype=np.float32))
@@ -928,7 +641,6 @@ def test_rank_one_passes_agree_with_full_passes(regime):
     same minimiser: two handles, one with JB_FLAG_NO_RANK_ONE, are stepped from IDENTICAL states (the reference handle's state
     is copied over every control step) and must agree to fp32 round-off amplified over 50 substeps - the same tolerance as
     against the oracle - in the ordinary regime and with half the robots on the floor."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n, task = 1024, "move_to_pose"
     a_env = JitterbugVecEnv(n, task, seed=6)
     b_env = JitterbugVecEnv(n, task, seed=6, flags=1)
@@ -943,7 +655,7 @@ def test_rank_one_passes_agree_with_full_passes(regime):
         if regime == "flat_out" and t < T - 50:
             continue                                        # let the robots tip over first, compare the last 50 steps
         ob, rb, _, _ = b_env.step(act)
-        good = np.abs(oa - ob) <= 1e-4 * np.abs(ob) + 1e-6
+        good = within(oa, ob)
         ok += good.sum(); tot += good.size
     print("rank-one vs full passes (%s): %.5f of entries within tolerance" % (regime, ok / tot))
     assert ok / tot >= 0.995
@@ -955,7 +667,6 @@ def test_wave_composition_invariance_in_the_tipped_regime():
     """An env's bits must not depend on its wave-mates - also when robots lie on a leg and the Newton loop runs its rare paths (spread
     sweeps, several full passes, rank-one passes, the replica's factorisation): 256 envs driven flat out for 250 control steps give the
     same observations bit for bit with 1, 2 and 4 envs per wave (chaotic by then: one differing bit anywhere would have grown)."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     n, steps = 256, 250
     out = {}
     for epw in (1, 2, 4):
@@ -980,7 +691,6 @@ def test_tuned_policies_reach_the_reference_bands():
     structure (heuristic_policies.py:28-56) with the parameters a cross-entropy search found SOLVES move_from_origin here (return >= 900,
     as the reference's DDPG agents do on MuJoCo: fig-rl-perf, median 940-950) and reaches on move_in_direction the top of the band the
     reference's MuJoCo agents occupy (median 330, p90 550-600: the task is NOT solved there either) - 0.05-0.065 m/s along the target."""
-    from jitterbug_amd.vec_env import JitterbugVecEnv
     PI = np.pi
 
     def wrap(a):

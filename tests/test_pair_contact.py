@@ -5,28 +5,10 @@ CPU tests of the oracle side: the narrow phase against MuJoCo's (MPR, restated i
 import numpy as np
 import pytest
 
-from jitterbug_amd import augmented_jitterbug as aj, model
+from jitterbug_amd import model
 from oracle import oracle as O
-
-
-def mass_touching_models():
-    """randomised models whose mass cannot turn freely (exact GJK sweep), with the leg each one hits"""
-    Ps = aj.augmented_params(600, seed=123)
-    cl = O.mass_sweep_clearance(Ps, 72)
-    bad = np.nonzero(cl <= 1e-9)[0]
-    assert 10 <= len(bad) <= 60          # ~3.6 % of the reference's draws
-    out = []
-    for i in bad[:16]:
-        hits = {}
-        for phi in np.linspace(0, 2 * np.pi, 145)[:-1]:
-            q = model.qpos0(Ps[i]); q[15] = phi
-            for l in range(4):
-                ok, d, n, pos = O.pair_geometric(Ps[i], q, l)
-                if ok and d < 0:
-                    hits.setdefault(l, []).append((phi, d))
-        assert hits, i
-        out.append((Ps[i], hits))
-    return out
+from tests.parity_inputs import conditioning_inputs, mass_touching_models, tiled
+from tests.parity_protocol import MARGIN_TOL, NARROW_RESID_TOL, NEAR_SWITCH_CAP, assert_protocol, host_pair_vs_oracle, protocol_message, teacher_forced
 
 
 @pytest.fixture(scope="module")
@@ -184,31 +166,13 @@ def test_nominal_model_is_untouched_by_the_pair_contact(params):
 
 
 # ----------------------------------------------------------------------------------------------- what the oracle reports about an env-step
-def _conditioning_inputs(touching):
-    """The inputs the per-env-model GPU tests run, as those tests build them (task, tables, env / action seed, steps, action stream), with the
-    share of env-steps whose deep flag the oracle sets - a property of the input alone (measured with the oracle, fp64, no kernel involved)."""
-    from tests.test_thread_contact import _small_actions, _touching_models
-    uniform = lambda rng, n: rng.uniform(-1, 1, size=n)
-    flat_out = lambda rng, n: np.ones(n)
-    mass = np.stack([touching[i % len(touching)][0] for i in range(64)])
-    thread_models = _touching_models(16, seed=11)
-    thread = np.stack([thread_models[i % len(thread_models)][0] for i in range(64)])
-    return [("nominal", "move_to_pose", model.default_params(), 256, 6, 200, uniform, 0.0),
-            ("augmented_params(256, seed=5)", "move_to_pose", aj.augmented_params(256, seed=5), 256, 6, 200, uniform, 0.0078),
-            ("mass-touching, uniform", "move_to_pose", mass, 64, 4, 300, uniform, 0.146),
-            ("mass-touching, flat out", "move_from_origin", mass, 64, 5, 150, flat_out, 0.111),
-            ("thread-touching, uniform", "move_to_pose", thread, 64, 4, 150, uniform, 0.0079),
-            ("thread-touching, small actions", "move_to_pose", thread, 64, 4, 150, _small_actions, 0.0)]
-
-
 def test_oracle_reports_deep_overlap_and_switch_margin_separately(touching):
     """jbo_stats.margin_min folds two conditions into one number: how close a contact candidate came to switching (the model's one
     discontinuity) and a pair overlap deeper than the leg's radius, which forces it to 0.  OracleEnv.conditioning() reports them apart:
     margins() == where(deep, 0, switch) EXACTLY on every env-step of every input, the per-source parts make up the switch margin, the nominal
     model is never deep, the mass - leg narrow phase's fixed counts leave a residual (`narrow_resid`) only on deep env-steps, and the deep share of each input is the one the GPU tests' bounds were derived from (+- 20 % relative: it is a
     property of the input, and the touching inputs must really exercise the class - a seventh of their env-steps)."""
-    from tests.test_gpu_parity import MARGIN_TOL, NARROW_RESID_TOL, NEAR_SWITCH_CAP
-    for name, task, P, n, seed, steps, actions, deep_share in _conditioning_inputs(touching):
+    for name, task, P, n, seed, steps, actions, deep_share in conditioning_inputs(touching):
         o = O.OracleEnv(n, task, P, seed=seed, per_env_model=P.ndim == 2)
         o.reset()
         rng = np.random.default_rng(seed)
@@ -236,43 +200,6 @@ def test_oracle_reports_deep_overlap_and_switch_margin_separately(touching):
 
 
 # ----------------------------------------------------------------------------------------------- the kernel source on the host, fp32
-def host_pair_vs_oracle(variant, P, task, seed, steps, flat_out=False, skip=0, actions=None, f32=1, groups=4, deep_only=False):
-    """The PAIR (`pair`) or LEAN + PAIR (`pair_lean`) instantiation of the kernel's substep, built for the host (tests/host_harness.cpp) in
-    fp32 with four lane groups, against the oracle, teacher-forced like tests/test_gpu_parity.py::_teacher_forced: one model per env, the
-    oracle's state handed to the host build every control step (split into hi + lo words like jb_set_state), observations compared.
-    Returns one row per env-step: env, step, switch margin, deep flag, entries outside 1e-4 rel + 1e-6 abs, entries outside the strict
-    1e-4 rel + 1e-5 abs, largest error, residual of the oracle's narrow phase; and how many steps raised the failure flag.  (tools/flip_study.py prints tables of these.)"""
-    import ctypes as C
-    import tests.build_harness as bh
-    lib = C.CDLL(bh.build())
-    dp = C.POINTER(C.c_double)
-    fn = getattr(lib, "jbh_step_" + variant)
-    fn.argtypes = [dp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp]
-    n = len(P)
-    o = O.OracleEnv(n, task, P, seed=seed, per_env_model=True)
-    o.reset()
-    rng = np.random.default_rng(seed)
-    rows, failed = [], 0
-    for t in range(-skip, steps):
-        a = np.ones(n) if flat_out else (rng.uniform(-1, 1, size=n) if actions is None else actions(rng, n))
-        if t < 0:                                       # lead-in on the oracle alone (robots tip over), not compared
-            o.step(a, auto_reset=False)
-            continue
-        q0, v0, tg = o.get_state()
-        oo, _, _ = o.step(a, auto_reset=False)
-        c = o.conditioning()
-        for i in range(n):
-            if deep_only and not c["deep"][i]:          # (a study of the deep class alone, on inputs where it is rare)
-                continue
-            Pi = np.ascontiguousarray(P[i]); q, v, fail = q0[i].copy(), v0[i].copy(), np.zeros(1)
-            assert fn(Pi.ctypes.data_as(dp), q.ctypes.data_as(dp), v.ctypes.data_as(dp), float(np.float32(a[i])), 50, 1, 20, f32, groups, 1, fail.ctypes.data_as(dp)) == 0
-            failed += int(fail[0] != 0)
-            q[3:7] /= np.linalg.norm(q[3:7])
-            err = np.abs(O.observation(Pi, task, q, v, tg[i]) - oo[i])
-            rows.append((i, t, c["switch"][i], c["deep"][i], (err > 1e-4 * np.abs(oo[i]) + 1e-6).sum(), (err > 1e-4 * np.abs(oo[i]) + 1e-5).sum(), err.max(), c["narrow_resid"][i]))
-    return np.array(rows, dtype=np.float64), failed
-
-
 @pytest.mark.parametrize("variant", ["pair", "pair_lean"])
 def test_host_fp32_pair_kernels_hold_the_strict_line_on_deep_overlaps(touching, variant):
     """The property the GPU tests hold the PAIR kernels to, on the CPU (so that a change of the kernel source meets it before it reaches a GPU):
@@ -281,8 +208,7 @@ def test_host_fp32_pair_kernels_hold_the_strict_line_on_deep_overlaps(touching, 
     entry of EVERY env-step of the well and the deep class; every env-step that is not has a switch margin below MARGIN_TOL (a contact
     that switched a substep earlier or later); and the deep class is really there (>= 5 % of the env-steps).  The deep class is where the
     narrow phase looks for the nearest surface point of the leg's axis INSIDE the mass; fp64 host tests cannot see an fp32-only defect there."""
-    from tests.test_gpu_parity import MARGIN_TOL          # the one constant (3 ulp of the 35 mm body height in fp32)
-    P = np.stack([touching[i % len(touching)][0] for i in range(64)])
+    P = tiled(touching, 64)
     for name, kw in (("uniform", dict(task="move_to_pose", seed=4, steps=60)), ("flat out", dict(task="move_from_origin", seed=5, steps=12, flat_out=True, skip=250))):
         rows, failed = host_pair_vs_oracle(variant, P, **kw)
         switch, deep, strict, worst = rows[:, 2], rows[:, 3] != 0, rows[:, 5], rows[:, 6]
@@ -302,10 +228,9 @@ def test_host_fp32_pair_kernels_hold_the_strict_line_on_deep_overlaps(touching, 
 def test_gpu_touching_models_match_the_oracle(touching):
     """One model per env, every one of them a robot whose mass hits a front leg: the PAIR kernel (chosen automatically for per-env
     models) against the oracle, teacher-forced, 300 control steps with the motor driven both ways and 150 with it flat out - the strict parity
-    protocol of tests/test_gpu_parity.py in full, the env-steps with the leg's axis inside the mass (the deep class) held like the others."""
-    from tests.test_gpu_parity import _teacher_forced, assert_protocol, protocol_message
-    P = np.stack([touching[i % len(touching)][0] for i in range(64)])
-    r = _teacher_forced("move_to_pose", 64, 300, seed=4, params=P)
+    protocol of tests/parity_protocol.py in full, the env-steps with the leg's axis inside the mass (the deep class) held like the others."""
+    P = tiled(touching, 64)
+    r = teacher_forced("move_to_pose", 64, 300, seed=4, params=P)
     print("touching models, uniform actions:", r)
     # every model here is a robot whose mass hits a leg, 50 of the 64 by more than the leg's radius at some time: 14.6 % of the env-steps are
     # of the DEEP class (jb_oracle.c collide()), held to the strict line like the well class - these are the env-steps in which the pair
@@ -313,7 +238,7 @@ def test_gpu_touching_models_match_the_oracle(touching):
     assert r["kernel_variant"] == "pair", r
     assert_protocol(r, well_bad=2, deep_share_min=0.05)
     assert r["frac"] >= 0.999, protocol_message(r)
-    r = _teacher_forced("move_from_origin", 64, 150, seed=5, params=P, flat_out=True)
+    r = teacher_forced("move_from_origin", 64, 150, seed=5, params=P, flat_out=True)
     print("touching models, motor flat out:", r)
     # motor flat out, 89 % of the robots lying on their legs, the mass hitting the leg at 150 rad/s: 11.1 % of the env-steps deep.  The same
     # lines as every other run: no entry of a well-conditioned or deep env-step off by 2e-5.
@@ -356,7 +281,7 @@ def test_gpu_pair_contact_is_really_simulated_and_chosen_by_the_model(touching):
         q, v, tg = a.get_state()
         a.set_state(q, v, tg); b.set_state(q, v, tg)
         oa, ra, _, _ = a.step(u); ob, rb, _, _ = b.step(u)
-        ok = np.abs(oa - ob) <= 1e-4 * np.abs(ob) + 2e-6
+        ok = np.abs(oa - ob) <= 1e-4 * np.abs(ob) + 2e-6          # (a bound of its own on purpose: two kernels against each other, a 2e-6 floor - not the protocol's within())
         worst = max(worst, np.abs(oa - ob).max())
         assert ok.mean() > 0.999, (t, ok.mean())
     print("nominal model, PAIR kernel vs ordinary kernel, step by step from common states: max |diff| %.2e" % worst)

@@ -6,6 +6,7 @@ import pytest
 
 from jitterbug_amd import _lib, model
 from jitterbug_amd import augmented_jitterbug as aj
+from tests.parity_protocol import MARGIN_TOL, NARROW_RESID_TOL, ParityTally, assert_protocol, free_running, teacher_forced, within
 
 ALL = dict(modify_legs=True, modify_mass=True, modify_coreBody1=True, modify_coreBody2=True, modify_global_density=True, modify_gear=True)
 COMBOS = [dict(), dict(modify_legs=True), dict(modify_mass=True), dict(modify_legs=True, modify_mass=True), dict(modify_coreBody1=True, modify_gear=True), ALL]
@@ -110,35 +111,17 @@ def test_device_compiler_matches_python_on_given_offsets_and_steps_like_the_orac
     np.testing.assert_allclose(out["params"], ref, rtol=1e-8, atol=1e-30)
     o = O.OracleEnv(n, "move_to_pose", ref, seed=6, per_env_model=True)
     np.testing.assert_allclose(env.reset(), o.reset(), rtol=2e-6, atol=2e-6)
-    from tests.test_gpu_parity import ParityTally, assert_protocol, protocol_message
-    rs, rs2 = np.random.default_rng(0), np.random.default_rng(1000)
-    tally = ParityTally(n, "move_to_pose", ref)
-    env2 = o2 = None
-    for t in range(30):
-        a = rs.uniform(-1, 1, size=n)
-        env.set_state(*o.get_state())
-        og, rg, _, _ = env.step(a)
-        oo, ro, _ = o.step(a, auto_reset=False)
-        ill_bad = tally.add(o, og, oo, rg, ro, env.get_state())
-        if ill_bad.any():
-            # the cascade check, on a second pair of envs with the same device-compiled models: the GPU's next step from its own state
-            if env2 is None:
-                env2 = JitterbugVecEnv(n, "move_to_pose", seed=6, auto_reset=False, time_limit=float("inf"))
-                env2.randomise_models(offsets=offs, **flags)
-                o2 = O.OracleEnv(n, "move_to_pose", ref, seed=6, per_env_model=True)
-                env2.reset(); o2.reset()
-            q2, v2, t2 = env.get_state()
-            env2.set_state(q2, v2, t2); o2.set_state(q2, v2, t2)
-            a2 = rs2.uniform(-1, 1, size=n)
-            tally.cascade(ill_bad, o2, env2.step(a2)[0], o2.step(a2, auto_reset=False)[0])
-    r = tally.result(env.counters()[2].sum())
+    env.close()
+
+    def device_compiled(**extra):          # (the cascade check's second env too: the same device-compiled models)
+        e = JitterbugVecEnv(n, "move_to_pose", seed=6, auto_reset=False, **extra)
+        e.randomise_models(offsets=offs, **flags)
+        return e
+    r = teacher_forced("move_to_pose", n, 30, seed=6, params=ref, make_env=device_compiled, action_seed=0)
     print("device-compiled models, 96 envs x 30 steps:", r)
     # the whole protocol.  2880 env-steps: the near-switch cap is 0.3 % plus three binomial spreads of a run this size (3 x 0.07 %) - this
     # test allowed 3 % of the env-steps outside its own 30 nm before
     assert_protocol(r, well_bad=0)
-    env.close()
-    if env2 is not None:
-        env2.close()
 
 
 @pytest.mark.gpu
@@ -218,38 +201,29 @@ def test_config5_shard_8192_device_models_against_the_oracle(variant):
     bad = np.zeros((3,), dtype=np.int64); tot_c = np.zeros((3,), dtype=np.int64); ill_c = np.zeros((3,), dtype=np.int64)
     rew_err = np.zeros(3); worst_c = np.zeros(3)
     per_step = []
-    from tests.test_gpu_parity import MARGIN_TOL, NARROW_RESID_TOL, ParityTally, assert_protocol, protocol_message
     tally = ParityTally(64, task, P[idx])
-    followed = np.zeros(64, bool)
-    for t in range(steps):
-        a = rng.uniform(-1, 1, size=n)
-        q, v, tg = env.get_state()
+
+    def account(t, pre, og, rg, oo, ro, o):
         if t % 4 == 0:
             for j, i in enumerate(idx):
                 for leg in range(4):
-                    okp, dist, _, _ = O.pair_geometric(P[i], q[i], leg)
+                    okp, dist, _, _ = O.pair_geometric(P[i], pre[0][i], leg)
                     if okp and dist < 0:
                         depth[j] = max(depth[j], -dist)
-        og, rg, dg, _ = env.step(a)
-        o.set_state(q[idx], v[idx], tg[idx])
-        oo, ro, do = o.step(a[idx], auto_reset=False)
-        # the GPU runs free, so the cascade check needs no second env: the near-switch env-steps that left the tolerance at step t are followed
-        # into step t + 1, which IS the GPU's next step from its own state
-        tally.cascade(followed, o, og[idx], oo)
-        followed = tally.add(o, og[idx], oo, rg[idx], ro, tuple(x[idx] for x in env.get_state()))
         cond = o.conditioning()
         # well and deep classes alike - but for the deep env-steps whose narrow phase stops short of its root, which the tally bounds (DEEP_ERROR_CAP)
         held = (cond["switch"] >= MARGIN_TOL) & ~(cond["deep"] & (cond["narrow_resid"] >= NARROW_RESID_TOL))
-        err = np.abs(og[idx].astype(np.float64) - oo)
-        w = err <= 1e-4 * np.abs(oo) + 1e-6
-        per_step.append((held.copy(), (~w).sum(1), err.max(1), np.abs(rg[idx] - ro), cond["deep"].copy(), cond["switch"] < MARGIN_TOL))
+        err = np.abs(og - oo)          # (fp32 - fp64: taken in fp64)
+        w = within(og, oo)
+        per_step.append((held.copy(), (~w).sum(1), err.max(1), np.abs(rg - ro), cond["deep"].copy(), cond["switch"] < MARGIN_TOL))
+    og = free_running(env, o, idx, steps, lambda t: rng.uniform(-1, 1, size=n), tally=tally, hook=account)
     cls = np.where(depth <= 0, 0, np.where(depth < LEG_RADIUS, 1, 2))
     deep_of_class = np.zeros(3, dtype=np.int64)
     for well, nbad, emax, rerr, deep, near in per_step:
         for c in range(3):
             deep_of_class[c] += (deep & (cls == c)).sum()
             m = (cls == c) & well
-            bad[c] += nbad[m].sum(); tot_c[c] += m.sum() * oo.shape[1]; ill_c[c] += ((cls == c) & near).sum()
+            bad[c] += nbad[m].sum(); tot_c[c] += m.sum() * model.OBS_DIM[task]; ill_c[c] += ((cls == c) & near).sum()
             if m.any():
                 worst_c[c] = max(worst_c[c], emax[m].max()); rew_err[c] = max(rew_err[c], rerr[m].max())
     sizes = [int((cls == c).sum()) for c in range(3)]

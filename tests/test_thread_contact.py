@@ -1,7 +1,7 @@
 """The second geom-geom contact randomised models can produce: the motor-axis THREAD (geom 20: a cylinder of 1 mm radius on the motor body,
 coaxial with the motor hinge, reference jitterbug.xml:105) against the upper-leg cylinders (jitterbug.xml:52, 65, 79, 92; every jitterbug
 geom has contype = conaffinity = 1).  With the reference's sigmas (augmented_jitterbug.py:165-241) the thread sits inside a front upper leg
-at rest in ~0.03 % of the draws; robots that do it are DRAWN here: the reference's distribution plus a motor offset that
+at rest in ~0.03 % of the draws; robots that do it are DRAWN (tests/parity_inputs.py thread_touching_models): the reference's distribution plus a motor offset that
 brings the thread to a front leg's shoulder."""
 import ctypes as C
 
@@ -10,42 +10,13 @@ import pytest
 
 from jitterbug_amd import augmented_jitterbug as aj, model
 from oracle import oracle as O
-
-
-def _touching_models(n, seed=0):
-    """draws of the reference's distribution whose motor offset is then moved so that the thread overlaps the upper leg of a front leg by a
-    few hundredths of a millimetre to half a millimetre at the rest pose (leg 0 or 1 = XML leg2 / leg3, alternating)"""
-    rng = np.random.RandomState(seed)
-    out = []
-    while len(out) < n:
-        off = aj.draw_offsets(rng, modify_legs=True, modify_mass=True)
-        leg = len(out) & 1
-        sx = 1.0 if leg == 0 else -1.0
-        want = -rng.uniform(2e-5, 5e-4)                    # overlap asked for
-        lo, hi = 0.0, 1.0                                  # move the motor axis along the line towards that leg's shoulder end
-        base = off[27:29].copy()
-        target = np.array([sx * 0.0046, 0.0068])
-        ok = False
-        for it in range(40):
-            mid = 0.5 * (lo + hi)
-            off[27:29] = base + mid * (target - base)
-            P = model.compile_spec(aj.apply_offsets(off, modify_legs=True, modify_mass=True))
-            d = O.pair_thread_geometric(P, model.qpos0(P), leg)[0]
-            if d > want:
-                lo = mid
-            else:
-                hi = mid
-            if abs(d - want) < 2e-6:
-                ok = True
-                break
-        if ok:
-            out.append((P, leg, d))
-    return out
+from tests.parity_inputs import small_actions, thread_touching_models, tiled
+from tests.parity_protocol import assert_protocol, protocol_message, teacher_forced
 
 
 @pytest.fixture(scope="module")
 def touching():
-    return _touching_models(12, seed=7)
+    return thread_touching_models(12, seed=7)
 
 
 def test_thread_flag_keeps_its_sign_apart_from_the_no_ellipsoid_sentinel(touching):
@@ -184,7 +155,7 @@ def test_both_pairs_of_one_leg_at_once_fp64_host_equals_oracle(touching):
 
 def test_captured_double_contact_states_with_lane_groups_fp64_host_equals_oracle():
     """Six env-steps captured from a GPU run (tests/golden/thread_double_contact_states.npy: step, env, action, qpos, qvel, target; models =
-    _touching_models(16, seed=11)[env % 16]) in which the mass and the thread touch one leg together.  With helper lane groups the two pair
+    thread_touching_models(16, seed=11)[env % 16]) in which the mass and the thread touch one leg together.  With helper lane groups the two pair
     slots sit in DIFFERENT groups, and the groups' active-set records are added up: with a plain sum of the 5-bit fields an edge entering one
     contact's set cancelled an edge leaving the other's, the check saw "no change" and the Newton iteration stopped one pass early (errors of
     1e-3 on these states).  The record now carries a per-slot multiplier (jb_sim.hpp contact_apply): 1, 2 and 4 groups = oracle."""
@@ -193,7 +164,7 @@ def test_captured_double_contact_states_with_lane_groups_fp64_host_equals_oracle
     lib = C.CDLL(bh.build())
     dp = C.POINTER(C.c_double)
     lib.jbh_step_pair.argtypes = [dp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp]
-    models = _touching_models(16, seed=11)
+    models = thread_touching_models(16, seed=11)
     S = np.load(os.path.join(os.path.dirname(__file__), "golden", "thread_double_contact_states.npy"))
     worst = 0.0
     for row in S:
@@ -223,7 +194,7 @@ def test_every_kernel_variant_on_random_orientations_fp64_host_equals_oracle():
     names = ("jbh_step_groups", "jbh_step_lean", "jbh_step_pair", "jbh_step_pair_lean")
     for name in names:
         getattr(lib, name).argtypes = [dp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp]
-    models = [m[0] for m in _touching_models(6, seed=11)] + [model.default_params()]
+    models = [m[0] for m in thread_touching_models(6, seed=11)] + [model.default_params()]
     rng = np.random.default_rng(9)
     worst, pair_seen, most = 0.0, 0, 0
     for trial in range(49):
@@ -259,23 +230,14 @@ def test_every_kernel_variant_on_random_orientations_fp64_host_equals_oracle():
     assert worst < 1e-10
 
 
-def _small_actions(rng, n):
-    """The motor held within a few degrees of its rest angle: on these robots - their motor axis sits 7 mm nearer a front leg than nominal - a
-    turning mass would strike that leg too (by millimetres: the deep-overlap class of tests/test_pair_contact.py); held back, the thread is
-    the only geom-geom contact, which is what this file is about."""
-    return rng.uniform(-0.02, 0.02, size=n)
-
-
 @pytest.mark.gpu
 def test_gpu_thread_contact_matches_the_oracle():
     """One model per env, every one a robot whose thread rubs a front upper leg: the PAIR kernel (chosen automatically for per-env models) and
-    LEAN + PAIR against the oracle, teacher-forced, 150 control steps - the strict parity protocol of tests/test_gpu_parity.py in full
+    LEAN + PAIR against the oracle, teacher-forced, 150 control steps - the strict parity protocol of tests/parity_protocol.py in full
     (the thread contact's own activation margin is part of the switch margin); the oracle's contact list shows the thread pair live
     and the mass pair not; and the same robots on the kernel WITHOUT the pair contacts (JB_FLAG_NO_PAIR) leave the tolerance."""
-    from tests.test_gpu_parity import _teacher_forced, assert_protocol, protocol_message
-    models = _touching_models(16, seed=11)
     n = 64
-    P = np.stack([models[i % len(models)][0] for i in range(n)])
+    P = tiled(thread_touching_models(16, seed=11), n)
     for flags, name in ((0, "pair"), (2, "lean_pair"), (8, "ordinary")):
         live = dict(thread=0, mass=0)
 
@@ -286,7 +248,7 @@ def test_gpu_thread_contact_matches_the_oracle():
                     geoms = [int(x) for x in d["con_geom"][:d["ncon"]]]
                     live["thread"] += any(x >= model.NGEOM + 4 for x in geoms)
                     live["mass"] += any(model.NGEOM <= x < model.NGEOM + 4 for x in geoms)
-        r = _teacher_forced("move_to_pose", n, 150, seed=4, params=P, flags=flags, actions=_small_actions, probe=probe, envs_per_wave=4 if flags == 2 else 0)
+        r = teacher_forced("move_to_pose", n, 150, seed=4, params=P, flags=flags, actions=small_actions, probe=probe, envs_per_wave=4 if flags == 2 else 0)
         print("thread-touching models, %s kernel: oracle samples with the thread pair live %d, with the mass pair live %d;" % (name, live["thread"], live["mass"]), r)
         assert r["kernel_variant"] == name
         assert live["thread"] >= 40 and live["mass"] == 0
@@ -305,12 +267,10 @@ def test_gpu_thread_and_mass_contacts_together():
     """The same robots with the motor turning: the mass strikes the leg the thread already rubs - both pair slots of one lane live in the
     same substeps (tests/test_thread_contact.py::test_both_pairs_... holds the kernel source to the oracle in fp64 there).  0.8 % of these
     env-steps are of the deep class (the leg's axis inside the mass), held like the others: the strict parity protocol of
-    tests/test_gpu_parity.py in full - PAIR and LEAN + PAIR."""
-    from tests.test_gpu_parity import _teacher_forced, assert_protocol, protocol_message
-    models = _touching_models(16, seed=11)
-    P = np.stack([models[i % len(models)][0] for i in range(64)])
+    tests/parity_protocol.py in full - PAIR and LEAN + PAIR."""
+    P = tiled(thread_touching_models(16, seed=11), 64)
     for flags in (0, 2):
-        r = _teacher_forced("move_to_pose", 64, 150, seed=4, params=P, flags=flags)
+        r = teacher_forced("move_to_pose", 64, 150, seed=4, params=P, flags=flags)
         print("thread-touching models, motor turning, flags %d:" % flags, r)
         assert_protocol(r, well_bad=6, worst_well=2e-5)      # measured: 2 (PAIR) / 1 (LEAN + PAIR), worst 6.5e-6
         assert r["deep_steps"] > 0 and r["frac"] >= 0.999, protocol_message(r)

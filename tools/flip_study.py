@@ -6,12 +6,12 @@ deep flag of the geom-geom pairs).
     python tools/flip_study.py --variant pair|pair_lean --inputs augmented|mass|thread [--envs N] [--steps K] [--seed S] [--task T]
                                [--flat-out] [--skip N] [--deep-only] [--sensitivity]     one model per env, PAIR / LEAN + PAIR kernel source
 Inputs as the GPU tests build them: augmented = augmented_params(N, seed=5); mass = the mass-touching models of
-tests/test_pair_contact.py tiled to N; thread = the thread-touching models of tests/test_thread_contact.py tiled to N.  --flat-out: motor
+tests/parity_inputs.py tiled to N; thread = its thread-touching models tiled to N.  --flat-out: motor
 flat out, --skip N: that many lead-in steps on the oracle alone (the robots tip over).  --deep-only: the host build runs the deep env-steps
 only (where they are rare).  --sensitivity: for every env-step of the well / deep classes outside the strict tolerance, the ORACLE's own
 step from the same state rounded to fp32 (what an fp32 simulator is handed, but for the height and the quaternion) against its step from
 the fp64 state - how much of the error is the conditioning of the step itself.
-Prints the three classes of tests/test_gpu_parity.py (well / deep / near-switch), the margin table, a per-env table and the outliers."""
+Prints the three classes of tests/parity_protocol.py (well / deep / near-switch), the margin table, a per-env table and the outliers."""
 import argparse
 import ctypes as C
 import os
@@ -24,7 +24,8 @@ sys.path.insert(0, ROOT)
 from jitterbug_amd import model  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 import tests.build_harness as bh  # noqa: E402
-from tests.test_gpu_parity import MARGIN_TOL, NARROW_RESID_TOL  # noqa: E402
+from tests.parity_inputs import mass_touching_models, thread_touching_models, tiled  # noqa: E402
+from tests.parity_protocol import MARGIN_TOL, NARROW_RESID_TOL, host_pair_vs_oracle, within  # noqa: E402
 
 BINS = ((0, 1e-9), (1e-9, 1e-8), (1e-8, 3e-8), (3e-8, 1e-7), (1e-7, 3e-7), (3e-7, 1e-6), (1e-6, 1e-5), (1e-5, 1))
 
@@ -55,7 +56,7 @@ def nominal(n, steps, task):
             qf, vf = hstep(q0[i], v0[i], np.float32(a[i]))          # (the harness splits the fp64 state into hi + lo words like jb_set_state)
             of = O.observation(P, task, qf, vf, tg[i])
             err = np.abs(of - oo[i])
-            ok = err <= 1e-4 * np.abs(oo[i]) + 1e-6
+            ok = within(of, oo[i])
             rows.append((mar[i], ok.mean(), err.max()))
     rows = np.array(rows)
     print("env-steps %d; entries within tolerance %.5f; env-steps fully within %.5f; worst %.3g" % (len(rows), rows[:, 1].mean(), (rows[:, 1] == 1).mean(), rows[:, 2].max()))
@@ -69,13 +70,7 @@ def models(inputs, n):
     from jitterbug_amd import augmented_jitterbug as aj
     if inputs == "augmented":
         return aj.augmented_params(n, seed=5)
-    if inputs == "mass":
-        from tests.test_pair_contact import mass_touching_models
-        ms = mass_touching_models()
-    else:
-        from tests.test_thread_contact import _touching_models
-        ms = _touching_models(16, seed=11)
-    return np.stack([ms[i % len(ms)][0] for i in range(n)])
+    return tiled(mass_touching_models() if inputs == "mass" else thread_touching_models(16, seed=11), n)
 
 
 def sensitivity(P, task, seed, steps, flat_out, skip, wanted):
@@ -98,7 +93,6 @@ def sensitivity(P, task, seed, steps, flat_out, skip, wanted):
 
 
 def pair(args):
-    from tests.test_pair_contact import host_pair_vs_oracle
     P = models(args.inputs, args.envs)
     rows, failed = host_pair_vs_oracle(args.variant, P, args.task, args.seed, args.steps, flat_out=args.flat_out, skip=args.skip, deep_only=args.deep_only)
     env, step, switch, deep, bad, strict, worst, resid = rows.T

@@ -4,7 +4,7 @@ on the GPU box); a MuJoCo trace in the same format would be consumed by the same
 
 move_from_origin: ONE env, 1000 control steps (a whole episode: exactly configs[0]); move_to_pose: 2 envs, 100 steps.  Seed 0,
 actions ~ U(-1, 1) from numpy default_rng(0).  Stored per step t: qpos/qvel/target BEFORE the step, the action, obs/reward AFTER it,
-and the oracle's contact-switch margin of the step (jbo_stats.margin_min, see tests/test_gpu_parity.py MARGIN_TOL)."""
+and the oracle's contact-switch margin of the step (jbo_stats.margin_min, see tests/parity_protocol.py MARGIN_TOL)."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

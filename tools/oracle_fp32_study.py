@@ -1,4 +1,4 @@
-"""Supporting evidence for the parity protocol's conditioning (tests/test_gpu_parity.py MARGIN_TOL): the ORACLE'S OWN algorithm - MuJoCo's
+"""Supporting evidence for the parity protocol's conditioning (tests/parity_protocol.py MARGIN_TOL): the ORACLE'S OWN algorithm - MuJoCo's
 pipeline as oracle/jb_oracle.c restates it: world-frame Jacobian dynamics, dense Cholesky, dense Newton contact solve - compiled in fp32
 (`#define double float` after the system headers; a throw-away build under oracle/_build, test infrastructure) and stepped teacher-forced
 against its fp64 build.  If a completely different fp32 implementation also fails the tolerance exactly on the env-steps that come within
@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from jitterbug_amd import model  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+from tests.parity_protocol import within  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 60
@@ -58,7 +59,7 @@ for t in range(steps):
         L.jbo_step_physics(P32.ctypes.data_as(fp), q.ctypes.data_as(fp), v.ctypes.data_as(fp), np.float32(a[i]), 50, C.byref(o), None, None)
         of = O.observation(P, task, q.astype(np.float64), v.astype(np.float64), tg[i])
         err = np.abs(of - oo[i])
-        rows.append((mar[i], (err <= 1e-4 * np.abs(oo[i]) + 1e-6).mean(), err.max()))
+        rows.append((mar[i], within(of, oo[i]).mean(), err.max()))
 rows = np.array(rows)
 print("fp32 build of the oracle's own algorithm vs its fp64 build, %d env-steps: entries within tolerance %.4f, env-steps fully within %.4f, worst %.3g"
       % (len(rows), rows[:, 1].mean(), (rows[:, 1] == 1).mean(), rows[:, 2].max()))

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from jitterbug_amd import model
 from jitterbug_amd.vec_env import JitterbugVecEnv
 from oracle import oracle as O
-from tests.test_gpu_parity import MARGIN_TOL
+from tests.parity_protocol import MARGIN_TOL, within
 task, n, steps, seed = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
 flat_out = len(sys.argv) > 5 and sys.argv[5] == "flat"
 skip = int(sys.argv[6]) if len(sys.argv) > 6 else 0
@@ -31,11 +31,11 @@ for t in range(-skip, steps):
     well = o.margins() >= MARGIN_TOL
     og = og.astype(np.float64)
     err = np.abs(og - oo)
-    bad = (err > 1e-4 * np.abs(oo) + 1e-6) & well[:, None]
+    bad = ~within(og, oo) & well[:, None]
     cnt += bad.sum(0)
     stat = globals().setdefault("stat", dict(bad_steps=0, bad_with_cap=0, cap_steps=0, cap_steps_bad=0))
     bs = bad.any(1)
-    stat["bad_steps"] += int(bs.sum()); stat["bad_with_cap"] += int((bs & (capd > 0)).sum()); stat["cap_steps"] += int((capd > 0).sum()); stat["cap_steps_bad"] += int(((capd > 0) & (err > 1e-4 * np.abs(oo) + 1e-6).any(1)).sum())
+    stat["bad_steps"] += int(bs.sum()); stat["bad_with_cap"] += int((bs & (capd > 0)).sum()); stat["cap_steps"] += int((capd > 0).sum()); stat["cap_steps_bad"] += int(((capd > 0) & (~within(og, oo)).any(1)).sum())
     for i, j in zip(*np.nonzero(bad)):
         if shown < 25:
             shown += 1

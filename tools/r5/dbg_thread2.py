@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from jitterbug_amd import model
 from jitterbug_amd.vec_env import JitterbugVecEnv
 from oracle import oracle as O
-from tests.test_thread_contact import _touching_models
+from tests.parity_inputs import thread_touching_models as _touching_models
 models = _touching_models(16, seed=11)
 n = 64
 P = np.stack([models[i % len(models)][0] for i in range(n)])
