@@ -12,6 +12,9 @@
 //                             tests/ run the very same source in fp32/fp64 against
 //                             the oracle without a GPU.  The host instantiation is
 //                             test infrastructure, not a product path.
+//
+// The device's quad / row exchanges are DPP moves with bound_ctrl set (dpp_mov below): only controls under which every
+// lane has a source lane - quad permutations and row rotations - may use it; see "DPP controls".
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -32,13 +35,33 @@
 
 namespace jb {
 
+// ----------------------------------------------------------------------------- DPP controls of the quad / row exchanges
+// Every exchange inside a quad or a 16-lane row below is ONE DPP move with full row and bank masks and bound_ctrl SET.  bound_ctrl
+// decides what a lane gets whose source lane does not exist (a shift past the end of its row): its destination's previous content
+// (clear: the builtin's "old" operand, tied to the destination) or zero (set).  A quad permutation and a row rotation have a source for
+// every lane, so the flag changes no value - but with it clear the register allocator must first put the "old" zero where the result
+// is wanted, which costs a v_mov_b32 before or a copy after nearly every move (profiles/ab_dpp_forms.txt).  A control that CAN leave a
+// lane without a source (row_shl / row_shr, wave shifts, row_bcast) needs the old value and must not go through dpp_mov: the
+// static_assert there refuses it.  (A source lane that EXEC disables reads as zero with the flag set; with it clear the write was
+// skipped and the tied zero stayed - the same value, so code under a partial EXEC mask sees what it saw before.)
+constexpr int DPP_QUAD_XOR1 = 0xB1, DPP_QUAD_XOR2 = 0x4E;      // quad_perm [1,0,3,2] / [2,3,0,1]
+constexpr int DPP_ROW_ROR4 = 0x124, DPP_ROW_ROR8 = 0x128;      // row_ror:4 / row_ror:8
+constexpr int dpp_quad_perm_ctrl(int s0, int s1, int s2, int s3) { return s0 | (s1 << 2) | (s2 << 4) | (s3 << 6); }      // lane l of a quad reads lane s_l
+constexpr int dpp_quad_rot_ctrl(int k) { return dpp_quad_perm_ctrl(k & 3, (k + 1) & 3, (k + 2) & 3, (k + 3) & 3); }    // lane l reads lane (l + k) & 3
+constexpr int dpp_quad_bcast_ctrl(int j) { return dpp_quad_perm_ctrl(j, j, j, j); }                                    // every lane reads lane j
+constexpr bool dpp_every_lane_has_a_source(int ctrl) { return (ctrl >= 0x00 && ctrl <= 0xFF) || (ctrl >= 0x121 && ctrl <= 0x12F); }      // quad_perm, row_ror:1-15
+
 // ----------------------------------------------------------------------------- scalar lanes (device)
 #if defined(__HIPCC__)
+template <int CTRL> JB_D int dpp_mov(int x) {
+    static_assert(dpp_every_lane_has_a_source(CTRL), "bound_ctrl would zero the lanes this control leaves without a source: pass the old value explicitly");
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true);
+}
 JB_D float dpp_quad_xor1(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+    return __builtin_bit_cast(float, dpp_mov<DPP_QUAD_XOR1>(__builtin_bit_cast(int, x)));  // quad_perm [1,0,3,2]
 }
 JB_D float dpp_quad_xor2(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+    return __builtin_bit_cast(float, dpp_mov<DPP_QUAD_XOR2>(__builtin_bit_cast(int, x)));  // quad_perm [2,3,0,1]
 }
 JB_D float quad_sum(float x) {
     x += dpp_quad_xor1(x);
@@ -46,8 +69,8 @@ JB_D float quad_sum(float x) {
     return x;
 }
 JB_D unsigned quad_sum_u(unsigned x) {
-    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);
-    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false);
+    x += (unsigned)dpp_mov<DPP_QUAD_XOR1>((int)x);
+    x += (unsigned)dpp_mov<DPP_QUAD_XOR2>((int)x);
     return x;
 }
 JB_D bool any_lane(bool m) { return __builtin_amdgcn_ballot_w64(m) != 0ull; }
@@ -59,8 +82,8 @@ JB_D unsigned xor_sum_bits(unsigned u, int off, bool sym2, bool is_float) {
     auto add = [&](unsigned a, unsigned b) { return is_float ? __builtin_bit_cast(unsigned, __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b)) : a + b; };
     if (off == 32) { auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false); return add(r[0], r[1]); }
     if (off == 16) { auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false); return add(r[0], r[1]); }
-    if (off == 8) return add(u, (unsigned)__builtin_amdgcn_update_dpp(0, (int)u, 0x128, 0xF, 0xF, false));             // row_ror:8
-    if (off == 4 && sym2) return add(u, (unsigned)__builtin_amdgcn_update_dpp(0, (int)u, 0x124, 0xF, 0xF, false));     // row_ror:4
+    if (off == 8) return add(u, (unsigned)dpp_mov<DPP_ROW_ROR8>((int)u));             // row_ror:8
+    if (off == 4 && sym2) return add(u, (unsigned)dpp_mov<DPP_ROW_ROR4>((int)u));     // row_ror:4
     return add(u, (unsigned)__shfl_xor((int)u, off, 64));
 }
 // Transposed sum over 4 helper groups that sit in the four 16-lane rows of the wave: row g returns the total of v[g],
@@ -81,7 +104,7 @@ JB_D float row_transpose_sum(float v0, float v1, float v2, float v3) {
 JB_D unsigned xor_get_bits(unsigned u, int off) {
     if (off == 32) { auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false); return r[1]; }      // (vsrc's lower half receives vdst's upper half)
     if (off == 16) { auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false); return r[1]; }      // (vsrc's even rows receive vdst's odd rows)
-    if (off == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)u, 0x128, 0xF, 0xF, false);      // row_ror:8
+    if (off == 8) return (unsigned)dpp_mov<DPP_ROW_ROR8>((int)u);      // row_ror:8
     return (unsigned)__shfl_xor((int)u, off, 64);
 }
 // ... exact for every lane (two more integer operations)
@@ -92,7 +115,7 @@ JB_D unsigned xor_get_any_u(unsigned u, int off) {
 }
 JB_D float xor_get(float x, int off) { return __builtin_bit_cast(float, xor_get_bits(__builtin_bit_cast(unsigned, x), off)); }
 JB_D unsigned xor_get_u(unsigned x, int off) { return xor_get_bits(x, off); }
-template <int J> JB_D float quad_bcast(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), J * 0x55, 0xF, 0xF, false)); }
+template <int J> JB_D float quad_bcast(float x) { return __builtin_bit_cast(float, dpp_mov<dpp_quad_bcast_ctrl(J)>(__builtin_bit_cast(int, x))); }
 JB_D float xor_sum(float x, int off, bool sym2) { return __builtin_bit_cast(float, xor_sum_bits(__builtin_bit_cast(unsigned, x), off, sym2, true)); }
 JB_D unsigned xor_sum_u(unsigned x, int off, bool sym2) { return xor_sum_bits(x, off, sym2, false); }
 JB_D unsigned wave_bcast_u(unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); }   // value of the first active lane
@@ -111,14 +134,12 @@ JB_D void wave_sync() {
 // ---- quad-level exchanges for the spread contact sweeps (jb_sim.hpp): a lane may work on a contact of ANOTHER leg of its env
 // quad_rot<K>: the value of lane (l + K) & 3 of the quad; quad_bcast_u: the value of lane j of the quad (DPP quad_perm, one instruction)
 template <int K> JB_D float quad_rot(float x) {
-    constexpr int ctrl = K == 1 ? 0x39 : K == 2 ? 0x4E : 0x93;      // quad_perm [1,2,3,0] / [2,3,0,1] / [3,0,1,2]
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xF, 0xF, false));
+    return __builtin_bit_cast(float, dpp_mov<dpp_quad_rot_ctrl(K)>(__builtin_bit_cast(int, x)));
 }
 template <int K> JB_D unsigned quad_rot_u(unsigned x) {
-    constexpr int ctrl = K == 1 ? 0x39 : K == 2 ? 0x4E : 0x93;
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, 0xF, 0xF, false);
+    return (unsigned)dpp_mov<dpp_quad_rot_ctrl(K)>((int)x);
 }
-template <int J> JB_D unsigned quad_bcast_u(unsigned x) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, J * 0x55, 0xF, 0xF, false); }
+template <int J> JB_D unsigned quad_bcast_u(unsigned x) { return (unsigned)dpp_mov<dpp_quad_bcast_ctrl(J)>((int)x); }
 JB_D unsigned quad_lane_id(const float*) { return threadIdx.x & 3u; }
 // element idx of the scratch column of lane `src` of the own quad (`me`: the own position in the quad)
 JB_D float ld_leg(const float* p, int stride, unsigned idx, unsigned src, unsigned me) { return p[(int)(idx * (unsigned)stride) + (int)src - (int)me]; }
@@ -126,8 +147,8 @@ JB_D void st_leg(float* p, int stride, unsigned idx, unsigned src, unsigned me, 
 // the value lane `src` of the quad holds
 JB_D float quad_pick(float x, unsigned src) {
     const int xi = __builtin_bit_cast(int, x);
-    const float x0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0x00, 0xF, 0xF, false)), x1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0x55, 0xF, 0xF, false));
-    const float x2 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0xAA, 0xF, 0xF, false)), x3 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, xi, 0xFF, 0xF, 0xF, false));
+    const float x0 = __builtin_bit_cast(float, dpp_mov<dpp_quad_bcast_ctrl(0)>(xi)), x1 = __builtin_bit_cast(float, dpp_mov<dpp_quad_bcast_ctrl(1)>(xi));
+    const float x2 = __builtin_bit_cast(float, dpp_mov<dpp_quad_bcast_ctrl(2)>(xi)), x3 = __builtin_bit_cast(float, dpp_mov<dpp_quad_bcast_ctrl(3)>(xi));
     // (bit tests, not a chain of `src == k ? ... :` - that becomes a switch on a per-lane value, one exec-masked block per case)
     const float lo = (src & 1u) ? x1 : x0, hi = (src & 1u) ? x3 : x2;
     return (src & 2u) ? hi : lo;
