@@ -6,6 +6,10 @@ from jitterbug_amd import augmented_jitterbug as aj, model
 from oracle import oracle as O
 
 
+# every row of the launch table (jb_variant.hpp STEP_ROWS: the 12 step-kernel instantiations) as (kernel variant, envs per wave)
+LAUNCH_ROWS = [(v, epw) for v, epws in (("ordinary", (1, 2, 4, 8)), ("pair", (1, 2, 4, 8)), ("lean", (1, 2, 4)), ("lean_pair", (4,))) for epw in epws]
+
+
 def mass_touching_models():
     """randomised models whose mass cannot turn freely (exact GJK sweep), with the leg each one hits"""
     Ps = aj.augmented_params(600, seed=123)

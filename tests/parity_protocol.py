@@ -228,6 +228,8 @@ def teacher_forced(task, n, steps, seed, contacts=True, params=None, flat_out=Fa
     `deep_strict_bad` (outside strict_within()) / `worst_deep` the same figures over the DEEP class, `clamped_*` over its env-steps with an
     unconverged narrow phase and `worst_deep_converged` over the others (see DEEP_ERROR_CAP); `ill_*` and `worst_ill` over the
     NEAR-SWITCH class alone (see MARGIN_TOL).  `flip_margin_max`: the largest SWITCH margin of an env-step outside the strict tolerance.
+    `resolved`: the main env's solver_stats() before it is closed - wave-substeps that went to the line-searched second solve (None where the
+    env under test has no such counter).
     actions(rng, n): another action stream than uniform / flat out; probe(t, q, v, a): called with the oracle's pre-step state.
     make_env(**extra): builds the env under test in place of the JitterbugVecEnv of these arguments - anything with reset, set_state, step,
     get_state, counters, kernel_variant and close; called for the main env (no keywords) and, when a cascade check is first needed, with the
@@ -277,12 +279,14 @@ def teacher_forced(task, n, steps, seed, contacts=True, params=None, flat_out=Fa
             tally.cascade(ill_bad, o2, og2, oo2)
     sc, ep, cap = g.counters()
     variant = g.kernel_variant
+    stats = getattr(g, "solver_stats", None)          # (an env under test without the counter - a host stand-in - reports None)
+    resolved = None if stats is None else int(stats())
     g.close()
     if g2 is not None:
         g2.close()
     q, _, _ = o.get_state()
     tipped = float(((1 - 2 * (q[:, 4] ** 2 + q[:, 5] ** 2)) < 0.5).mean())
-    return tally.result(cap.sum(), tipped=tipped, kernel_variant=variant)
+    return tally.result(cap.sum(), tipped=tipped, kernel_variant=variant, resolved=resolved)
 
 
 def free_running(env, o, idx, steps, actions, tally=None, hook=None):

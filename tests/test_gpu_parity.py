@@ -8,7 +8,7 @@ import pytest
 from jitterbug_amd import model
 from jitterbug_amd.vec_env import JitterbugVecEnv
 from oracle import oracle as O
-from tests.parity_inputs import thread_touching_models
+from tests.parity_inputs import LAUNCH_ROWS, thread_touching_models
 from tests.parity_protocol import (ILL_ERROR_CAP, MARGIN_TOL, assert_protocol, assert_rewards, free_running, protocol_message,
                                    teacher_forced, within)
 
@@ -284,9 +284,6 @@ def test_all_geoms_contact_parity(variant):
     _, _, cap = g.counters()
     assert cap.sum() == 0
     g.close()
-
-
-LAUNCH_ROWS = [(v, epw) for v, epws in (("ordinary", (1, 2, 4, 8)), ("pair", (1, 2, 4, 8)), ("lean", (1, 2, 4)), ("lean_pair", (4,))) for epw in epws]
 
 
 @pytest.mark.parametrize("variant,epw", LAUNCH_ROWS, ids=["%s-%d" % r for r in LAUNCH_ROWS])

@@ -640,6 +640,48 @@ def test_line_searched_solve_settles_rounding_level_cycles_fp32(params):
     assert st[0] >= 4 and st[3] == 0, st          # the cycling records did go through the second solve, and it settled every one
 
 
+def test_failure_counter_counts_second_solves_that_end_at_their_cap(params):
+    """The counter behind "every contact solve converged" (LaneState::fail; LEAN: SC_LSTATE + 34 in the scratch) moves only in the cold block,
+    when the line-searched solve itself ends at NEWTON_LS_CAP.  A build with -DJB_LS_CAP=1 gives that solve ONE outer pass, max_newton = 1
+    sends every substep whose set does not repeat at once to it: on tipped robots the returned counter must move, and by exactly the number of
+    second solves that ended at the cap (jbh_ls_stats' fourth entry), env-step by env-step, in the ordinary and in the LEAN layout (fp64, four
+    lane groups).  Only this host library is built with the define."""
+    import tests.build_harness as bh
+    lib = C.CDLL(bh.build(defines={"JB_LS_CAP": 1}))
+    dp = C.POINTER(C.c_double)
+    lib.jbh_ls_stats.argtypes = [C.POINTER(C.c_long), C.c_int]
+    for f in (lib.jbh_step_groups, lib.jbh_step_lean):
+        f.argtypes = [dp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+    P = np.ascontiguousarray(params, dtype=np.float64)
+    st = (C.c_long * 4)()
+    env = _contact_states(params, 10, tipped=True)
+    q0, v0, _ = env.get_state()
+    assert ((1 - 2 * (q0[:, 4] ** 2 + q0[:, 5] ** 2)) < 0.5).any()          # some robots really lie on the floor
+    counts = {}
+    for name, fn, aux in (("ordinary", lib.jbh_step_groups, 1), ("ordinary, no aux bodies", lib.jbh_step_groups, 0), ("lean", lib.jbh_step_lean, 0)):
+        lib.jbh_set_aux(aux)
+        try:
+            per_env = []
+            for i in range(10):
+                q, v, fail = q0[i].copy(), v0[i].copy(), np.zeros(1)
+                lib.jbh_ls_stats(st, 1)
+                assert fn(P.ctypes.data_as(dp), q.ctypes.data_as(dp), v.ctypes.data_as(dp), 1.0, 50, 1, 1, 0, 4, 1, fail.ctypes.data_as(dp)) == 0
+                lib.jbh_ls_stats(st, 1)
+                assert fail[0] == st[3] and st[3] <= st[0] <= 50, (name, i, fail[0], list(st))          # one env per call: a capped wave is a capped env
+                assert np.isfinite(q).all() and np.isfinite(v).all()
+                per_env.append(int(fail[0]))
+        finally:
+            lib.jbh_set_aux(1)
+        counts[name] = per_env
+    print("substeps per env-step whose second solve ended at a cap of one pass:", counts)
+    lying = (1 - 2 * (q0[:, 4] ** 2 + q0[:, 5] ** 2)) < 0.5
+    for name, per_env in counts.items():          # the counter moved, on a robot lying on the floor too (one that rests there settles at once and may count nothing)
+        assert any(c > 0 for c in per_env) and any(c > 0 for c, l in zip(per_env, lying) if l), counts
+    # without the aux bodies (which sum the motor / root terms in another order) the two layouts run the same arithmetic on the host: the
+    # counter kept in the scratch says what the counter kept in a register says
+    assert counts["lean"] == counts["ordinary, no aux bodies"], counts
+
+
 # ---------------------------------------------------------------------------------------------- the step-kernel variants (jb_variant.hpp)
 VARIANT_ORDINARY, VARIANT_PAIR, VARIANT_LEAN, VARIANT_LEAN_PAIR = 0, 1, 2, 3          # include/jitterbug_hip.h JB_VARIANT_*
 # (variant, envs per wave, one model per env) -> bytes of dynamic LDS of the launch.  Provenance: launch_step's own expression in jb_api.hip as
