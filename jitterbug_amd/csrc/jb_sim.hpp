@@ -1613,7 +1613,8 @@ JB_HD void pair_narrow(const Vec3<V>& ce, const Mat3<V>& Re, const Vec3<V>& sz, 
 // pointing outwards, and the multiplier's own equation satisfied); a lane that did not takes the cold scheme's result instead - its own
 // data decide, never its wave-mates'.  The first substep of a control step always runs the cold scheme (the warm state is not part of
 // the simulator's state: K single steps and one K-step launch must agree bit for bit).  The oracle keeps the cold scheme: both converge
-// to the same contact to round-off.
+// to the same contact to fp32 round-off.  In fp64 they part on deep contacts, where the cold counts stop short of the root this one reaches
+// (0.54 mm into a leg of 0.61 mm radius: 1e-8 in the normal, 5e-10 in the velocities after a substep; tests/test_hinge_range_cpu.py).
 template <typename V>
 JB_HD typename lane_traits<V>::mask pair_narrow_warm(const Vec3<V>& ce, const Mat3<V>& Re, const Vec3<V>& sz, const Vec3<V>& cc, const Vec3<V>& ua, const V& rad, const V& half,
                                                       V& t, V& lam, V& dist, Vec3<V>& n, Vec3<V>& pos) {
@@ -2350,12 +2351,24 @@ JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
         using W = Pk2<V>;
         Vec3<V> a1 = ldv3(m, LM_A1), e1 = ldv3(m, LM_E1);
         V s1, c1, s2, c2;
+#ifdef JB_HINGE_SINCOS_WIDE        // diagnostic host builds: every hinge through the wide routine (fp64: libm), no series anywhere
+        vsincos_pi(s.th1, s1, c1); vsincos_pi(s.th2, s2, c2);
+#else
         {
             W sn, cs;
             sincos_small(W(s.th1, s.th2), sn, cs);
             s1 = pk_lo(sn); s2 = pk_hi(sn); c1 = pk_lo(cs); c2 = pk_hi(cs);
         }
-        if (any_lane(mand(lane_ok, mor(gt(vabs(s.th1), V(0.9)), gt(vabs(s.th2), V(0.9)))))) { vsincos_pi(s.th1, s1, c1); vsincos_pi(s.th2, s2, c2); }      // (the quarter-turn reduction: good to 1e-7 for any angle a hinge can reach, and no libm slow path in the kernel)
+        // Beyond 0.9 rad the quarter-turn reduction (within 1e-7 of libm for any angle a hinge can reach - 8.4e-8 at worst over [-2 pi, 2 pi],
+        // tests/test_hinge_range_cpu.py - and no libm slow path in the kernel).  The BRANCH is wave-uniform, the CHOICE is each angle's own: the two routines are different polynomials with different
+        // bits, so an angle at or below 0.9 keeps the series' bits whatever its leg-mates and wave-mates hold.
+        const MK wide1 = gt(vabs(s.th1), V(0.9)), wide2 = gt(vabs(s.th2), V(0.9));
+        if (any_lane(mand(lane_ok, mor(wide1, wide2)))) {
+            V sw1, cw1, sw2, cw2;
+            vsincos_pi(s.th1, sw1, cw1); vsincos_pi(s.th2, sw2, cw2);
+            s1 = sel(wide1, sw1, s1); c1 = sel(wide1, cw1, c1); s2 = sel(wide2, sw2, s2); c2 = sel(wide2, cw2, c2);
+        }
+#endif
         V sp, cp;
         vsincos_pi(s.phi, sp, cp);
         if (o.aux) { s1 = sel(ax_motor, sp, s1); c1 = sel(ax_motor, cp, c1); }      // the motor's angle is wrapped to [-pi, pi): its own sine / cosine routine
@@ -2542,6 +2555,9 @@ JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                     // for the lanes that have none or did not converge from it
                     V wt = sc.ld(sc.pd + 9), wlam = sc.ld(sc.pd + 10);
                     MK warm_ok = mand(near_pair, gt(sc.ld(sc.pd + 11), V(0.5)));
+#ifdef JB_PAIR_NARROW_COLD         // diagnostic host builds: every substep takes the cold scheme, the one the oracle runs (jb_oracle.c pair_geometric)
+                    warm_ok = lt(V(1), V(0));
+#endif
                     if (any_lane(warm_ok)) {
                         const MK conv = pair_narrow_warm<V>(pe, Re, ldc3(m, LM_PE_S), uc, ua, ldc(m, LM_UC_R), uh, wt, wlam, pdist, pn, ppos);
                         // ... and only where the overlap is shallower than the leg's radius.  Deeper (the leg's axis inside the mass) the cold

@@ -305,6 +305,11 @@ extern "C" int jbh_substep_record(const double* P, const float* rec, int max_new
     if (fail_out) *fail_out = s_final.fail.v[0];
     return 0;
 }
+// The two fp32 sine / cosine routines of the hinge angles on n given angles: which = 0 jb_sim.hpp sincos_small (the series, |th| <= 0.9),
+// 1 jb_lane.hpp vsincos_pi (the quarter-turn reduction).  As this build compiles them: one rounding per operation, nothing fused.
+extern "C" void jbh_hinge_sincos_f32(int which, int n, const float* x, float* s, float* c) {
+    for (int i = 0; i < n; i++) { if (which) vsincos_pi(x[i], s[i], c[i]); else sincos_small<float>(x[i], s[i], c[i]); }
+}
 // jb_variant.hpp for the tests.  out = [JB_VARIANT_* id or -1 (no kernel), bytes of dynamic LDS, main lanes, lane groups, offload, aux, split tables,
 // scratch floats per lane, pd, pd2, red_lds, waves per SIMD, floats per lane of the block in global memory]; then, from jb_sim.hpp, what the
 // layout is stated in: [SC_PD, SC_PD_LEAN, SC_PD2 - SC_OVC, 4 * (NSLOT - ROW_K), SC_COUNT, SC_COUNT_LEAN, SC_COUNT_LEAN_PAIR].  Returns out[0].

@@ -1,5 +1,8 @@
 """The model draws and action streams the parity tests and the record runs under tools/ share: robots whose eccentric mass or motor-axis thread
 touches a front leg (why: tests/test_pair_contact.py, test_thread_contact.py), the per-env-model GPU tests' inputs.  Not a conftest: plain helpers."""
+import ctypes
+import functools
+
 import numpy as np
 
 from jitterbug_amd import augmented_jitterbug as aj, model
@@ -59,6 +62,97 @@ def thread_touching_models(n, seed=0):
         if ok:
             out.append((P, leg, d))
     return out
+
+
+HINGE_FAMILIES = (0.3, 0.85, 1.5, 2.8)      # H: leg hinges uniform in +-H rad.  The kernel source switches at 0.3 (all-geom path), 0.4 (thread broad phase) and 0.9 (sine / cosine routine)
+HINGE_SWITCHES = (0.3, 0.4, 0.9)
+ROOT_MOTOR_GEOMS = (0, 1, 2, 3, 20, 21)
+UPPER_LEG_GEOMS = tuple(g + 4 * l for l in range(4) for g in (4, 5))
+HINGE_FIRST_GEOMS = (tuple(range(22)), UPPER_LEG_GEOMS, ROOT_MOTOR_GEOMS)      # whose first floor contact state i starts from: by i % 3
+
+
+def _contact_geoms(P, q, v, opts, dbg):
+    """the geoms of the oracle's contacts at a state (O.forward_debug's con_geom, without the rest of its report: this runs ~10^5 times)"""
+    O.lib().jbo_forward_debug(O._p(P), O._p(q), O._p(v), 0.0, ctypes.byref(opts), ctypes.byref(dbg))
+    return dbg.con_geom[:dbg.ncon]
+
+
+def _upper_leg_alone(c):
+    return any((4 + 4 * l in c or 5 + 4 * l in c) and 6 + 4 * l not in c and 7 + 4 * l not in c for l in range(4))
+
+
+@functools.lru_cache(maxsize=None)
+def hinge_range_inputs(family, kind, n=256, seed=0, depth=(0.0002, 0.002)):
+    """hinge_range_states for the two model sets the hinge-range tests use, computed once per process (seconds each): kind "nominal" (one
+    table, the oracle's geom-geom pairs off: the kernels without PAIR) or "augmented" (augmented_params(n, seed=5), one model per state,
+    pairs on).  -> (P, q, v, contacts); the arrays are shared: do not write to them."""
+    P = model.default_params() if kind == "nominal" else aj.augmented_params(n, seed=5)
+    q, v, contacts = hinge_range_states(family, n, seed, P, depth=depth, pair_contacts=0 if kind == "nominal" else 3)
+    for a in (P, q, v):
+        a.setflags(write=False)
+    return P, q, v, contacts
+
+
+def hinge_range_states(family, n, seed, models, depth=(0.0002, 0.002), pair_contacts=3):
+    """n states with the leg hinges anywhere in +-family rad, each pushed into the floor: the construction of test_all_geoms_contact_parity
+    (uniform quaternion, motor in +-3 rad, its velocity scales, a bisection on the oracle for the height of the first floor contact) and then
+    a depth uniform in `depth` below it.  The first contact is any geom's (state i with i % 3 == 0), an upper-leg geom's (1) or a root-body /
+    motor-body geom's (2): a foot reaches the floor first in nearly every pose, and the upper legs and the bodies are what the hinge angle
+    moves between the kernel's paths.  The poses of class 1 are drawn on the robot's back (within some 20 degrees, not uniformly), and again
+    (at most 100 times) until some leg lies on its upper part alone, its lower leg and foot clear of the floor.
+    models: one table, or [n, NPARAM] (one per state).  pair_contacts: the oracle's geom-geom pairs (off for the kernels that do not
+    simulate them).  -> (q [n, 16], v [n, 15], per state the list of the oracle's contact geoms).
+    Conditions (hinge_range_conditions, checked by tests/test_hinge_range_cpu.py with the oracle alone): at n = 256 every family has at
+    least 40 states of each of the two kinds, and hinges on both sides of every switch below its H."""
+    assert family in HINGE_FAMILIES
+    rng = np.random.default_rng([seed, int(round(family * 100))])
+    P = np.asarray(models, dtype=np.float64)
+    Pi = (lambda i: P[i]) if P.ndim == 2 else (lambda i: P)
+    o = O.default_opts(pair_contacts=pair_contacts)
+    q = np.stack([model.qpos0(Pi(i)) for i in range(n)])
+    v = np.zeros((n, 15))
+    contacts, dbg = [], O.Debug()
+    for i in range(n):
+        below = rng.uniform(depth[0], depth[1])
+        Pm, qi, vi, first = np.ascontiguousarray(Pi(i)), q[i], v[i], set(HINGE_FIRST_GEOMS[i % 3])          # (qi, vi: views of the rows)
+        for attempt in range(100):
+            quat = rng.normal(size=4)
+            q[i, 3:7] = quat / np.linalg.norm(quat)
+            q[i, 7:15] = rng.uniform(-family, family, size=8)
+            q[i, 15] = rng.uniform(-3, 3)
+            v[i] = rng.normal(size=15) * np.array([.05] * 3 + [1] * 3 + [1] * 8 + [20])
+            if i % 3 == 1:          # on its back, within some 20 degrees and with any twist: the shortest rotation that takes `down` to -ez, then any angle about ez
+                down = np.array([0, 0, 1.0]) + 0.35 * rng.normal(size=3)
+                down /= np.linalg.norm(down)
+                turn = np.array([1 - down[2], -down[1], down[0], 0.0])
+                turn /= np.linalg.norm(turn)
+                psi = rng.uniform(-np.pi, np.pi)
+                cz, sz = np.cos(psi / 2), np.sin(psi / 2)
+                q[i, 3:7] = (cz * turn[0] - sz * turn[3], cz * turn[1] - sz * turn[2], cz * turn[2] + sz * turn[1], cz * turn[3] + sz * turn[0])
+            lo, hi = -0.1, 0.2
+            for _ in range(30):          # the height at which the first floor contact (of the state's class) appears
+                q[i, 2] = mid = 0.5 * (lo + hi)
+                if first.intersection(_contact_geoms(Pm, qi, vi, o, dbg)):
+                    lo = mid
+                else:
+                    hi = mid
+            q[i, 2] = lo - below
+            c = _contact_geoms(Pm, qi, vi, o, dbg)
+            if i % 3 != 1 or _upper_leg_alone(c):
+                break
+        contacts.append(c)
+    return q, v, contacts
+
+
+def hinge_range_conditions(family, q, contacts):
+    """What hinge_range_states' doc promises of a family at n = 256, from the oracle's contact lists alone: (states with an upper-leg cylinder
+    or knee tip (geoms 4+4l, 5+4l) on the floor and no lower-leg or foot geom (6+4l, 7+4l) of that leg, states with a root-body or
+    motor-body geom on the floor, hinges on both sides of every switch below the family's H)."""
+    upper_only = sum(_upper_leg_alone(c) for c in contacts)
+    root_motor = sum(any(g in ROOT_MOTOR_GEOMS for g in c) for c in contacts)
+    a = np.abs(q[:, 7:15])
+    both_sides = all((a < s).any() and (a > s).any() for s in HINGE_SWITCHES if s < family)
+    return upper_only, root_motor, both_sides
 
 
 def tiled(models, n):
