@@ -290,7 +290,7 @@ __device__ __forceinline__ void step_body(KArgs a, StepIO io) {
     s.st_xtra = 0.f; s.st_sweeps = 0.f; s.st_contact = 0.f; s.st_slots = 0.f; s.st_fast = 0.f; s.st_checks = 0.f;
 #endif
     SimOpts o; o.contacts = a.contacts; o.max_newton = a.max_newton; o.implicit_damp = 1; o.rank_one = a.rank_one; o.lean = LEAN ? 1 : 0; o.offload = OFFLOAD ? 1 : 0; o.spread = a.spread; o.prof = nullptr; o.hist = nullptr;
-    o.aux = aux_on ? 1 : 0; o.fuse_rows = LAY.fused_row_build ? 1 : 0;
+    o.aux = aux_on ? 1 : 0; o.fuse_rows = LAY.fused_row_build ? 1 : 0; o.every_lane_update = LAY.every_lane_update ? 1 : 0;
 #ifdef JB_CAPTURE
     o.capture = a.capture; o.capture_count = a.capture_count;
 #endif

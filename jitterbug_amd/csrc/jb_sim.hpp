@@ -54,6 +54,16 @@
 #define JB_PROF_ADD(o, i) ((void)0)
 #endif
 
+// No lane-GROUP predicate on register-only work: where registers are assigned under `is_main` / `grp == 0 || g1z` and the lanes that skip
+// hold values nobody reads afterwards, every lane makes the assignment - a skipping lane's old value would otherwise stay alive across the
+// update and cost a copy per value (tools/asm_copies.py, tools/experiments/group_liveness.txt).  Stores keep their predicates.
+// JB_GROUP_PREDICATED_MERGES: the reference form, the assignment under its group predicate (A/B measurements and tests/test_group_liveness_cpu.py).
+#ifdef JB_GROUP_PREDICATED_MERGES
+#define JB_GROUP_MERGE(pred) (pred)
+#else
+#define JB_GROUP_MERGE(pred) true
+#endif
+
 #ifndef JB_ROW_K
 #define JB_ROW_K 9          // cached contact rows per substep (SC_ROWS); a build parameter for A/B measurements and for the tests of the beyond-the-cache path
 #endif
@@ -1422,7 +1432,10 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
 #pragma unroll
             for (int k = 0; k < NQ4; k++) sc.st(SC_RED + 4 * k + sc.grp, row_transpose_sum(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]));
             wave_sync();          // every group's totals are in the scratch
-            if (sc.grp == 0 || g1z) {
+            // Every lane reloads (the scratch addresses are mirrored per group: the same words the main lanes read).  The other groups' partial
+            // sums are dead from here on - nobody reads their star_solve - and a reload under the group predicate would keep all of them alive
+            // across the swaps above, which overwrite both operands: a copy per input.  No lane-group predicate on register-only work.
+            if (JB_GROUP_MERGE(sc.grp == 0 || g1z)) {
                 const int src = g1z ? SC_ZERO : SC_RED;        // per lane: the same loads, another base address
 #pragma unroll
                 for (int i = 0; i < (PAIR ? 53 : 52); i++) v[i] = sc.ld(src + i);
@@ -1756,6 +1769,8 @@ struct SimOpts {
                          //    several: "spread sweeps" below); 0: diagnostic, the ordinary sweep only
     int fuse_rows = 1;   // 1: the contact rows are built by the first full sweep of the substep's hot solve (contact_sweep `build`); 0: in a pass of
                          //    their own before it (StepLayout::fused_row_build: the variants that would spill).  Same arithmetic, same bits.
+    int every_lane_update = 1;   // 1: the iterate's update after star_solve (newton_phase) is made by every lane, only its stores by the main lanes; 0: under
+                         //    the main lanes' predicate (StepLayout::every_lane_update: the variants that would spill).  Same arithmetic, same bits.
     float* capture = nullptr;           // diagnostic builds (-DJB_CAPTURE): ring of JB_CAPTURE_SLOTS records x 64 floats - the entry state of substeps whose contact solve stayed
     unsigned* capture_count = nullptr;  //   unconverged after the line-searched pass (substep_impl), and how many there were
     unsigned long long* prof;   // diagnostic builds: per-wave cycle accumulators [phaseA, check sweeps, full sweeps, solves, integrate]
@@ -2131,7 +2146,9 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                         ls_alpha = sel(whole, V(1), al * V(1.001) + V(1e-6));
                         wave_sync();      // (the mailbox is the reduction hand-over of the next full sweep)
                     }
-                    if (is_main) {
+                    // The iterate's update is register-only work: every lane makes it (the helper groups on whatever they hold - nobody reads
+                    // theirs, and the final pass takes the iterate from the scratch), only the stores below stay with the main lanes.
+                    if (JB_GROUP_MERGE(is_main) && (o.every_lane_update || is_main)) {
                         // envs whose active set already repeated keep their (exact) solution, rank-one envs theirs
                         const MK take = mand(unconverged, mnot(fast_env));
                         if (LS) {      // the step to the minimum of the cost along the Newton direction
@@ -2145,19 +2162,23 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                             nym = sel(part, ym + ls_alpha * (nym - ym), nym);
                             ls_flags = mbit(mand(take, part)) + mbit(mand(take, ls_tiny)) * 2u;
 #if !defined(__HIPCC__)
-                            if (g_ls_trace) {
+                            if (is_main && g_ls_trace) {
                                 V ty[6], tn[6];
                                 for (int i = 0; i < 6; i++) { ty[i] = v6get(yr, i); tn[i] = v6get(nyr, i); }
                                 ls_trace_pass(it, ls_alpha, take, ls_tiny, ty, tn, yl, nyl, ym, nym);
                             }
-                            g_ls_stats[1]++;
-                            if (any_lane(mand(take, part))) g_ls_stats[2]++;
+                            if (is_main) {
+                                g_ls_stats[1]++;
+                                if (any_lane(mand(take, part))) g_ls_stats[2]++;
+                            }
 #endif
                         }
 #pragma unroll
                         for (int ip = 0; ip < 3; ip++) yr[ip] = selw(take, nyr[ip], yr[ip]);
                         yl[0] = sel(take, nyl[0], yl[0]); yl[1] = sel(take, nyl[1], yl[1]); ym = sel(take, nym, ym);
                         fac_valid = mnot(fast_env);         // a rank-one env's factorisation is one edge behind its set
+                    }
+                    if (is_main) {
                         store_root(SC_Y, yr);
                         sc.st(SC_Y + 6, yl[0]); sc.st(SC_Y + 7, yl[1]); sc.st(SC_Y + 8, ym);
                     }
@@ -2178,17 +2199,19 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                     if (is_main) s.st_checks = s.st_checks + V(1);
 #endif
                     unsigned fin = 0u, full = 1u;
-                    if (is_main) {
+                    if (JB_GROUP_MERGE(is_main)) {      // (the records' comparison is register-only: every lane; the votes below keep to the main lanes)
                         MK changed = mor(mor(neq_u(acc.bw0, prev_bw0), neq_u(acc.bw1, prev_bw1)), neq_u(acc.xh, prev_xh));
                         unconverged = neq_u(quad_sum_u(mbit(changed)), zero_u<V>());
 #if !defined(__HIPCC__)
-                        if (LS && g_ls_trace) ls_trace_check(it, unconverged, acc.bw0, prev_bw0, acc.bw1, prev_bw1, acc.xh, prev_xh);
+                        if (is_main && LS && g_ls_trace) ls_trace_check(it, unconverged, acc.bw0, prev_bw0, acc.bw1, prev_bw1, acc.xh, prev_xh);
 #endif
                         if (LS) {      // the last update came from the line search
                             const MK shortened = neq_u(and_u(ls_flags, zero_u<V>() + 1u), zero_u<V>()), settled = neq_u(and_u(ls_flags, zero_u<V>() + 2u), zero_u<V>());
                             ls_flags = mbit(mand(shortened, mnot(unconverged))) * 4u;
                             unconverged = mand(mor(unconverged, shortened), mnot(settled));
                         }
+                    }
+                    if (is_main) {
 #if defined(JB_WAVE_STATS) && defined(__HIPCC__)
                                             if (!LS && o.hist && !xtra) {      // how many active-set bits flipped per unconverged env (ordinary substeps: exact records)
                                                 const unsigned fl = quad_sum_u((unsigned)__builtin_popcount(acc.bw0 ^ prev_bw0));
@@ -2253,7 +2276,7 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                     JB_PROF_ADD(o, 7);
                     if (final_pass || full_pass) break;
                     if (is_main) {      // rank-one passes only: their iterates go to the scratch for the next check
-                        fac_valid = mand(fac_valid, mnot(fast_env));
+                        fac_valid = mand(fac_valid, mnot(fast_env));      // (left under the predicate: taking it out changes no count - tools/experiments/group_liveness.txt)
                         store_root(SC_Y, yr);
                         sc.st(SC_Y + 6, yl[0]); sc.st(SC_Y + 7, yl[1]); sc.st(SC_Y + 8, ym);
                     }

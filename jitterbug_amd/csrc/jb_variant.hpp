@@ -31,6 +31,8 @@ struct StepLayout {
     bool fused_row_build;    // the first full Newton sweep of a substep builds the contact rows it applies (SimOpts::fuse_rows); false: the rows are
                              // built in a pass of their own before the solve - the rows whose register budget the fused sweep does not fit (it
                              // adds scratch operations to their substep loop's hot part: tools/asm_spills.py).  Same bits either way.
+    bool every_lane_update;  // the iterate's update after star_solve is made by every lane, not under the main lanes' predicate (SimOpts::every_lane_update,
+                             // tools/experiments/group_liveness.txt); false: the two rows whose hot part it would give scratch operations.  Same bits.
 };
 
 constexpr StepLayout step_layout(int epw, bool lean, bool pair) {
@@ -50,6 +52,7 @@ constexpr StepLayout step_layout(int epw, bool lean, bool pair) {
     l.ovc_floats = lean ? OVC_FLOATS_PER_LANE : 0;
     l.waves_per_simd = lean ? 2 : 1;
     l.fused_row_build = !(lean && pair) && !(pair && epw == 1) && !(!pair && !lean && epw == 8);
+    l.every_lane_update = !(lean && !pair && epw == 2) && !(!pair && !lean && epw == 8);
     return l;
 }
 
@@ -123,6 +126,7 @@ JB_HD SimOpts sim_opts(const StepLayout& l, int contacts, int max_newton, int im
     SimOpts o;
     o.contacts = contacts; o.max_newton = max_newton; o.implicit_damp = implicit_damp; o.rank_one = rank_one; o.spread = spread;
     o.lean = l.lean ? 1 : 0; o.offload = l.offload ? 1 : 0; o.aux = l.aux ? 1 : 0; o.fuse_rows = l.fused_row_build ? 1 : 0;
+    o.every_lane_update = l.every_lane_update ? 1 : 0;
     o.prof = nullptr; o.hist = nullptr;
     return o;
 }
