@@ -1,10 +1,10 @@
 """What do the quad / row exchanges of jb_lane.hpp cost in the hot part of a step kernel's substep loop - separate DPP moves, the copies
 behind them, the wait states in front of them - and which instruction consumes each move that the compiler left unfolded?
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -mllvm -disable-vector-combine -w -S --cuda-device-only -o /tmp/jb.s jitterbug_amd/csrc/jb_api.hip
+    python tools/asm_listing.py -o /tmp/jb.s
     python tools/asm_dpp_forms.py /tmp/jb.s [kernel-name-substring] [--consumers]
 
-One line per step kernel (the hot part as tools/asm_spills.py delimits it: the substep loop without its cold block): instructions,
+One line per step kernel (the hot part of tools/asm_listing.py: the substep loop without its cold block): instructions,
 v_mov_b32_e32, v_mov_b32_dpp, the folded DPP forms (v_add_f32_dpp and the like), s_nop, scratch operations, and the number of DPP moves
 whose result is next copied by a plain v_mov_b32_e32 (the copy a tied "old" operand forces; must be 0).  With --consumers, the unfolded
 moves by DPP control and by the first instruction that reads their result."""
@@ -12,37 +12,7 @@ import collections
 import re
 import sys
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-path = args[0]
-want = args[1] if len(args) > 1 else "jb_step_kernel"
-consumers = "--consumers" in sys.argv
-lines = open(path).read().split("\n")
-starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_Z\S+:", l)]
-ends = [i for i, l in enumerate(lines) if l.startswith(".Lfunc_end")]
-is_inst = re.compile(r"^\s+(v_|s_|ds_|global_|scratch_|buffer_|flat_)")
-
-
-def hot_part(body):
-    """indices (into body) of the instructions of the substep loop outside its cold block: tools/asm_spills.py's rule"""
-    inst_idx = [j for j, l in enumerate(body) if is_inst.match(l)]
-    labels = {}
-    for j, l in enumerate(body):
-        m = re.match(r"^(\.LBB\d+_\d+):", l)
-        if m:
-            labels[m.group(1)] = j
-    loops = []
-    for j, l in enumerate(body):
-        m = re.match(r"^\s+s_c?branch\S*\s+(\.LBB\d+_\d+)", l)
-        if m and m.group(1) in labels and labels[m.group(1)] < j:
-            loops.append((labels[m.group(1)], j))
-    loops.sort(key=lambda ab: ab[0] - ab[1])
-    outer = loops[0] if loops else (0, len(body))
-    inner = [ab for ab in loops[1:] if ab[0] >= outer[0] and ab[1] <= outer[1]]
-    sub = inner[0] if inner else outer
-    cb = [j for j, l in enumerate(body) if "jb-cold-solve-begin" in l]
-    ce = [j for j, l in enumerate(body) if "jb-cold-solve-end" in l]
-    cold = (cb[0], ce[-1]) if cb and ce else (-1, -1)
-    return [j for j in inst_idx if sub[0] <= j <= sub[1] and not cold[0] <= j <= cold[1]]
+import asm_listing
 
 
 def regs(tok):
@@ -61,12 +31,9 @@ def operands(l):
     return parts[0], ops
 
 
-for (i0, name), i1 in zip(starts, ends):
-    if want not in name:
-        continue
-    body = lines[i0:i1]
-    hot = hot_part(body)
-    text = [body[j] for j in hot]
+def forms(fn):
+    """(counts, unfolded moves by DPP control, unfolded moves by consumer) over the hot part of one function"""
+    text = [fn.body[j] for j in fn.hot]
     n = collections.Counter()
     by_ctrl, by_use = collections.Counter(), collections.Counter()
     for k, l in enumerate(text):
@@ -102,9 +69,15 @@ for (i0, name), i1 in zip(starts, ends):
                 use = "overwritten"
                 break
         by_use[use] += 1
-    short = re.sub(r"^_ZN12_GLOBAL__N_1\d+", "", name)[:36]
-    print("%-36s hot part: insts %6d  v_mov_b32_e32 %4d  v_mov_b32_dpp %4d  folded *_dpp %4d  s_nop %4d  scratch %3d  accvgpr %4d  dpp moves copied next %3d" % (
-        short, n["insts"], n["mov"], n["mov_dpp"], n["folded"], n["nop"], n["scratch"], n["accvgpr"], n["copied"]))
-    if consumers:
-        print("    unfolded moves by control : " + ", ".join("%s %d" % kv for kv in by_ctrl.most_common()))
-        print("    unfolded moves by consumer: " + ", ".join("%s %d" % kv for kv in by_use.most_common()))
+    return n, by_ctrl, by_use
+
+
+if __name__ == "__main__":
+    args, opts = asm_listing.cli(sys.argv[1:])
+    for fn in asm_listing.parse(*args[:2]):
+        n, by_ctrl, by_use = forms(fn)
+        print("%-36s hot part: insts %6d  v_mov_b32_e32 %4d  v_mov_b32_dpp %4d  folded *_dpp %4d  s_nop %4d  scratch %3d  accvgpr %4d  dpp moves copied next %3d" % (
+            fn.short[:36], n["insts"], n["mov"], n["mov_dpp"], n["folded"], n["nop"], n["scratch"], n["accvgpr"], n["copied"]))
+        if "--consumers" in opts:
+            print("    unfolded moves by control : " + ", ".join("%s %d" % kv for kv in by_ctrl.most_common()))
+            print("    unfolded moves by consumer: " + ", ".join("%s %d" % kv for kv in by_use.most_common()))
