@@ -256,6 +256,33 @@ int64_t jb_snapshot_host_bytes(jb_handle* h);
 int jb_snapshot(jb_handle* h, void* blob);
 int jb_restore(jb_handle* h, const void* blob, int64_t blob_bytes, const int32_t* src /*[N] nullable, host*/);
 int jb_score_tapes_device(jb_handle* h, int32_t n_steps, const float* d_tapes /*[K,N] nullable*/, float gamma, float* d_returns /*[N]*/, int32_t* d_alive /*[N] nullable*/);
+/* Readout (additive in ABI 5): where everything is.  One launch maps a state - the handle's current one, or a stack of snapshots - to, per
+ * env-state and in fp32:
+ *   frames    [JB_NFRAME, 12]  [pos(3) | R(9) row major]; R takes frame-local vectors to world vectors (MuJoCo's xmat).
+ *                              0-9    the ten moving bodies in include/jitterbug_model.h's order: pos = centre of mass in the world
+ *                                     (MuJoCo's xipos), R = the body's rotation from its orientation at qpos0
+ *                              10-31  the 22 geoms in the parameter table's order: pos = geom centre, R = geom frame (a cylinder's axis is
+ *                                     column 2)
+ *                              32     the target: pos = (tx, ty, target z), R = rotation about z by the target yaw
+ *   clearance [22]             signed smallest height of the geom's surface above the plane z = 0, metres; negative: the geom reaches below
+ *                              the floor.  The step kernels make their own activation tests: within a few nanometres of the plane the two
+ *                              roundings of the same height may differ in sign.
+ *   body_vel  [10, 6]          world linear velocity of each body's centre of mass, then the body's world angular velocity
+ *   energy    [8]              [P(3) | L(3) about the world origin | T | V]: total linear and angular momentum, kinetic energy, potential
+ *                              energy (gravity plus the nine hinge springs)
+ * from the state blocks (the low-order words of the height and the quaternion included) and the constant tables the handle holds (one
+ * shared, or one per env).  The pass reads the state and never writes it.
+ *   jb_readout_device  d_snaps: n_snaps snapshots of N envs each, back to back (jb_snapshot_bytes apart), or NULL = the handle's current
+ *                      state (n_snaps must then be 1).  Env-state k * N + j is env j of snapshot k and takes env j's table.  Each output
+ *                      is device memory for n_snaps * N env-states, or NULL: an absent output costs no stores.  The result for one
+ *                      env-state does not depend on what else is in the launch.  Asynchronous on the handle's stream.  JB_E_INVALID,
+ *                      and nothing is launched: n_snaps < 1, all four outputs NULL, a jb_step_async pending.
+ *   jb_readout         host buffers (each nullable, not all), the current state, synchronous; the device staging belongs to the handle and
+ *                      only grows. */
+#define JB_NFRAME 33
+int jb_readout_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_snaps, float* d_frames /*[n_snaps*N,33,12]*/, float* d_clearance /*[n_snaps*N,22]*/,
+                      float* d_body_vel /*[n_snaps*N,10,6]*/, float* d_energy /*[n_snaps*N,8]*/);
+int jb_readout(jb_handle* h, float* frames /*[N,33,12]*/, float* clearance /*[N,22]*/, float* body_vel /*[N,10,6]*/, float* energy /*[N,8]*/);
 /* seconds each wave of the LAST step launch was alive (one wave = jb_envs_per_wave envs), out[0 .. min(n_waves, max_waves)); returns the
  * number of waves.  Mean against maximum is the load imbalance of the launch (roofline). */
 int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves);

@@ -27,6 +27,7 @@
 #include "jb_model_compile.hpp"
 #include "jb_nominal_spec.h"
 #include "jb_owned.hpp"
+#include "jb_readout.hpp"
 #include "jb_sim.hpp"
 #include "jb_snapshot.hpp"
 #include "jb_step.hpp"
@@ -45,6 +46,9 @@ namespace {
 enum RootF : int { RF_P = 0, RF_Q = 3, RF_V = 7, RF_W = 10, RF_PHI = 13, RF_PHID = 14, RF_TURNS = 15, RF_WA = 16, RF_WL = 19, RF_WM = 22, RF_FAIL = 23, RF_TGT = 24, RF_LO = 27 /*5: low-order words of z and the quaternion*/, ROOT_F = 32 };
 enum LegF : int { LF_TH1 = 0, LF_TH2 = 1, LF_THD1 = 2, LF_THD2 = 3, LF_WJ0 = 4, LF_WJ1 = 5, LEG_F = 6 };
 static_assert(ROOT_F == SNAP_ROOT_F && LEG_F == SNAP_LEG_F, "jb_snapshot.hpp copies exactly the state blocks declared here");
+static_assert(RO_RF_P == RF_P && RO_RF_Q == RF_Q && RO_RF_V == RF_V && RO_RF_W == RF_W && RO_RF_PHI == RF_PHI && RO_RF_PHID == RF_PHID && RO_RF_TGT == RF_TGT && RO_RF_LO == RF_LO &&
+              RO_LF_TH1 == LF_TH1 && RO_LF_TH2 == LF_TH2 && RO_LF_THD1 == LF_THD1 && RO_LF_THD2 == LF_THD2, "jb_readout.hpp reads exactly the state fields declared here");
+static_assert(RO_NFRAME == JB_NFRAME, "the header promises this many frames");
 
 struct KArgs {
     int n, task, substeps, step_limit, auto_reset, contacts, max_newton, random_pose, per_env_model;
@@ -748,6 +752,7 @@ struct jb_handle {
     Dev<float> d_capture; Dev<unsigned> d_capture_count;      // diagnostic builds (-DJB_CAPTURE)
     Dev<float> d_tape, d_rows_stage, d_rew_stage;      // staging of the host-buffer rollouts (jb_step_many, jb_rollout_policy): grow-only
     Dev<unsigned char> d_done_stage;                   // jb_score_tapes_device: the done flags of every step, next to d_rew_stage (grow-only)
+    Dev<float> d_readout_stage;                        // jb_readout: the outputs on their way to the host (grow-only)
     Dev<uint32_t> d_snap_stage; Dev<int> d_src_stage;  // jb_snapshot / jb_restore: the raw blocks and the index map on their way to / from the host (grow-only)
     Dev<int> d_wave_order;           // launch order of the waves (jb_wave_order_kernel), empty while the device holds the whole batch at once
     int wave_slots;                  // waves the device holds at once with this handle's kernel variant
@@ -1279,7 +1284,7 @@ int jb_release_staging(jb_handle* h) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
     h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset(); h->d_done_stage.reset();
-    h->d_snap_stage.reset(); h->d_src_stage.reset();
+    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset();
     return JB_OK;
 }
 // ---------------------------------------------------------------------------------------------- snapshot / restore / fork, tape scoring
@@ -1384,6 +1389,49 @@ int jb_score_tapes_device(jb_handle* h, int32_t n_steps, const float* d_tapes, f
     hipLaunchKernelGGL(jb_return_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, (const float*)h->d_rew_stage.get(), (const unsigned char*)h->d_done_stage.get(),
                        (int)n_steps, (int)N, gamma, d_returns, (int*)d_alive);
     JB_HIP(hipGetLastError());
+    return JB_OK;
+}
+// The readout pass (jb_readout.hpp): one launch over n_snaps * N env-states, a quad of lanes each; reads the state, writes only its outputs.
+int jb_readout_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, float* d_frames, float* d_clearance, float* d_body_vel, float* d_energy) {
+    JB_ENTER(h);
+    if (n_snaps < 1) return fail(JB_E_INVALID, "jb_readout_device: n_snaps must be >= 1");
+    if (!d_frames && !d_clearance && !d_body_vel && !d_energy) return fail(JB_E_INVALID, "jb_readout_device: all four outputs are NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_readout_device: a jb_step_async is pending (jb_step_wait first)");
+    if (!d_snaps && n_snaps != 1) return fail(JB_E_INVALID, "jb_readout_device: the handle's current state is ONE state (n_snaps must be 1 without a snapshot stack)");
+    RoctxRange range("jb_readout");
+    const int N = h->cfg.n_envs;
+    RoArgs a;
+    a.first = d_snaps ? snap_view(const_cast<void*>(d_snaps), N) : state_view(h);      // (const_cast: the pass only reads)
+    a.stride_words = (long long)SNAP_WORDS * N;
+    a.total = (long long)n_snaps * N;
+    a.tab = h->ka.lane_model; a.n_tab = h->ka.per_env_model ? N : 1;
+    a.frames = d_frames; a.clear = d_clearance; a.bvel = d_body_vel; a.energy = d_energy;
+    a.vec4 = ((((uintptr_t)d_frames | (uintptr_t)d_clearance | (uintptr_t)d_body_vel | (uintptr_t)d_energy) & 15u) == 0) ? 1 : 0;
+    const long long blocks = (a.total + RO_EPB - 1) / RO_EPB;
+    if (blocks > 0x7fffffffLL) return fail(JB_E_INVALID, "jb_readout_device: too many env-states for one launch");
+    hipLaunchKernelGGL(jb_readout_kernel, dim3((unsigned)blocks), dim3(64), 0, h->stream, a);
+    JB_HIP(hipGetLastError());
+    return JB_OK;
+}
+int jb_readout(jb_handle* h, float* frames, float* clearance, float* body_vel, float* energy) {
+    JB_ENTER(h);
+    if (!frames && !clearance && !body_vel && !energy) return fail(JB_E_INVALID, "jb_readout: all four outputs are NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_readout: a jb_step_async is pending (jb_step_wait first)");
+    const size_t N = (size_t)h->cfg.n_envs;
+    int rc = grow_stage(h, h->d_readout_stage, N * (size_t)(RO_FRAMES + RO_CLEAR + RO_BVEL + RO_ENERGY), "the readout");
+    if (rc) return rc;
+    // (laid out [frames | body_vel | energy | clearance]: the first three lengths are multiples of four floats, so every part starts on a 16-byte word)
+    float* d_fr = h->d_readout_stage.get();
+    float* d_bv = d_fr + N * RO_FRAMES;
+    float* d_en = d_bv + N * RO_BVEL;
+    float* d_cl = d_en + N * RO_ENERGY;
+    rc = jb_readout_device(h, nullptr, 1, frames ? d_fr : nullptr, clearance ? d_cl : nullptr, body_vel ? d_bv : nullptr, energy ? d_en : nullptr);
+    if (rc) return rc;
+    if (frames) JB_HIP(hipMemcpyAsync(frames, d_fr, sizeof(float) * N * RO_FRAMES, hipMemcpyDeviceToHost, h->stream));
+    if (clearance) JB_HIP(hipMemcpyAsync(clearance, d_cl, sizeof(float) * N * RO_CLEAR, hipMemcpyDeviceToHost, h->stream));
+    if (body_vel) JB_HIP(hipMemcpyAsync(body_vel, d_bv, sizeof(float) * N * RO_BVEL, hipMemcpyDeviceToHost, h->stream));
+    if (energy) JB_HIP(hipMemcpyAsync(energy, d_en, sizeof(float) * N * RO_ENERGY, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
 // how long each wave of the last step launch lived, in seconds (s_memrealtime, 100 MHz): out[0 .. n_waves); returns the number of waves

@@ -73,7 +73,19 @@ class _NamedData:
             return R.reshape(-1) if comp is None else R["xyz".index(comp[0]), "xyz".index(comp[1])]
 
         self.qpos, self.qvel, self.xmat = _Indexer(qpos), _Indexer(qvel), _Indexer(xmat)
-        self.geom_xpos = _Indexer(lambda k: {"target": ph.target_position_xyz()}[k])
+        # world poses of every geom and body from the batch readout (JitterbugVecEnv.readout, float32 rows of this env); 'target' keeps its own path
+        def frame_row(names, first, what):
+            def get(k):
+                if k not in names:
+                    raise KeyError("%s has no %r: valid names are %s" % (what, k, ", ".join(names)))
+                return ph._frames()[first + names.index(k)]
+            return get
+
+        geom_row = frame_row(model.GEOM_NAMES + ("target",), model.FRAME_GEOM0, "geom_xpos / geom_xmat")
+        body_row = frame_row(model.BODY_NAMES, 0, "xipos")
+        self.geom_xpos = _Indexer(lambda k: ph.target_position_xyz() if k == "target" else geom_row(k)[0:3].copy())
+        self.geom_xmat = _Indexer(lambda k: geom_row(k)[3:12].copy())
+        self.xipos = _Indexer(lambda k: body_row(k)[0:3].copy())
         self.xquat = _Indexer(lambda k: {"target": ph.target_position_quat(), "jitterbug": ph._state()[0][3:7]}[k])
         self.xpos = _Indexer(lambda k: {"target": ph.target_position_xyz(), "jitterbug": ph._state()[0][0:3]}[k])
         self.sensordata = _Indexer(lambda k: {"jitterbug_framelinvel": ph.jitterbug_framelinvel()}[k])
@@ -103,6 +115,13 @@ class Physics:
             self._cache = (q[self._i], v[self._i], t[self._i])
             self._cache_version = self._venv.state_version
         return self._cache
+
+    def _frames(self):
+        """this env's [33, 12] frame rows of the batch readout, cached like the state"""
+        if getattr(self, "_frames_cache", None) is None or self._frames_version != self._venv.state_version:
+            self._frames_cache = self._venv.readout(frames=True, clearance=False)["frames"][self._i]
+            self._frames_version = self._venv.state_version
+        return self._frames_cache
 
     @property
     def _params(self):

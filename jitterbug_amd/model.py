@@ -41,6 +41,16 @@ BODY_PARENT = (-1, 0, 1, 0, 3, 0, 5, 0, 7, 0)
 BODY_NAMES = ("jitterbug", "leg2upper", "leg2lower", "leg3upper", "leg3lower",
               "leg1upper", "leg1lower", "leg4upper", "leg4lower", "mass")
 
+# the 22 collidable geoms in the parameter table's order: the XML's own name where it has one (jitterbug.xml:44-107; of a leg's four geoms
+# only the foot is named there), else <leg><part>_cyl / <leg>_tip
+GEOM_NAMES = (("coreBody1", "coreBody2", "screw1", "screw2")
+              + tuple(n for leg in model_spec.LEG_NAMES for n in (leg + "upper_cyl", leg + "_tip", leg + "lower_cyl", "foot" + leg[3:]))
+              + ("threadMass", "mass"))
+FOOT_GEOMS = tuple(7 + 4 * l for l in range(NLEG))      # the foot spheres, in model_spec.LEG_NAMES order
+# rows of a readout's `frames` (jb_readout): the ten bodies, the 22 geoms, the target
+NFRAME = NBODY + NGEOM + 1
+FRAME_GEOM0, FRAME_TARGET = NBODY, NBODY + NGEOM
+
 TASKS = ("move_from_origin", "face_direction", "move_in_direction", "move_to_position", "move_to_pose")
 OBS_DIM = dict(move_from_origin=15, face_direction=16, move_in_direction=19, move_to_position=18, move_to_pose=19)
 

@@ -1,0 +1,67 @@
+"""Recorded trajectories: a stack of device snapshots and the world poses read out of it.
+
+`record(venv, n_steps, actions)` steps a JitterbugVecEnv, takes a device snapshot before the first step and after every step (232 bytes
+per env each, one launch) into one buffer, and runs ONE readout over the whole stack (JitterbugVecEnv.readout_device): frame k is what a
+live readout after step k would have given, bit for bit.  `Trajectory.save_npz` writes chosen envs' frames with the geom shapes and the
+names - everything a viewer needs, none in particular: no renderer is in scope.
+
+torch carries the device buffers, as in jitterbug_amd.planning; the hot paths are the library's own kernels."""
+import numpy as np
+
+from . import model
+
+
+class Trajectory:
+    """frames [K+1, N, 33, 12] and clearance [K+1, N, 22] (float32 torch device tensors; rows as JitterbugVecEnv.readout gives them),
+    snapshots [K+1, snapshot_bytes] (uint8: the stack itself - restore_device row k to continue from step k) and the packed rows
+    [K, N, D+2] = [obs | reward | done] of the steps."""
+
+    def __init__(self, frames, clearance, snapshots, rows, params):
+        self.frames, self.clearance, self.snapshots, self.rows = frames, clearance, snapshots, rows
+        self._params = params          # env index -> float64[NPARAM] table that env was simulated with
+
+    @property
+    def n_steps(self):
+        return int(self.frames.shape[0]) - 1
+
+    def save_npz(self, path, envs):
+        """Write envs `envs` (a list of indices): frames [K+1, E, 33, 12], clearance [K+1, E, 22], geom_type [E, 22]
+        (0 sphere, 1 cylinder, 2 box, 3 ellipsoid) and geom_size [E, 22, 3] from the envs' model tables, frame_names [33], geom_names [22],
+        body_names [10], envs [E]."""
+        envs = [int(e) for e in envs]
+        P = np.stack([np.asarray(self._params(e), dtype=np.float64) for e in envs])
+        g = P[:, model.P_GEOM:model.P_GEOM + model.NGEOM * model.GEOM_STRIDE].reshape(len(envs), model.NGEOM, model.GEOM_STRIDE)
+        idx = self.frames.new_tensor(envs).long()
+        np.savez(path, frames=self.frames.index_select(1, idx).cpu().numpy(), clearance=self.clearance.index_select(1, idx).cpu().numpy(),
+                 geom_type=g[:, :, model.G_TYPE].astype(np.int32), geom_size=g[:, :, model.G_SIZE:model.G_SIZE + 3].copy(),
+                 frame_names=np.array(model.BODY_NAMES + model.GEOM_NAMES + ("target",)), geom_names=np.array(model.GEOM_NAMES),
+                 body_names=np.array(model.BODY_NAMES), envs=np.array(envs, dtype=np.int64))
+
+
+def record(venv, n_steps, actions=None):
+    """Step `venv` n_steps times - with the action tape `actions` [n_steps, N], or with the task's heuristic policy evaluated in the step
+    kernel when None - and return the Trajectory.  The steps are the ordinary single-step launches: the env ends in the state, and with
+    the rows, n_steps calls of step would have produced; snapshots and the readout only read."""
+    import torch
+    K, N = int(n_steps), venv.num_envs
+    assert K >= 0
+    dev = torch.device("cuda", int(venv.cfg.device_id))
+    cur = torch.cuda.current_stream(dev)
+    env_stream = torch.cuda.ExternalStream(int(venv.stream), device=dev) if venv.stream else torch.cuda.default_stream(dev)
+    nb = venv.snapshot_bytes
+    snaps = torch.empty((K + 1, nb), dtype=torch.uint8, device=dev)
+    rows = torch.empty((K, N, venv.obs_dim + 2), dtype=torch.float32, device=dev)
+    frames = torch.empty((K + 1, N, model.NFRAME, 12), dtype=torch.float32, device=dev)
+    clearance = torch.empty((K + 1, N, model.NGEOM), dtype=torch.float32, device=dev)
+    tape = None
+    if actions is not None:
+        tape = torch.as_tensor(np.ascontiguousarray(np.asarray(actions, dtype=np.float32).reshape(K, N))).to(dev)
+    env_stream.wait_stream(cur)          # (the tape was copied on the current stream)
+    venv.snapshot_device(snaps[0].data_ptr())
+    for k in range(K):
+        venv.step_many_device(1, None if tape is None else tape[k].data_ptr(), rows[k].data_ptr())
+        venv.snapshot_device(snaps[k + 1].data_ptr())
+    venv.readout_device(frames.data_ptr(), clearance.data_ptr(), snaps_ptr=snaps.data_ptr(), n_snaps=K + 1)
+    cur.wait_stream(env_stream)
+    venv.synchronize()
+    return Trajectory(frames, clearance, snaps, rows, venv.model_params)

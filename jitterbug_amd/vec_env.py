@@ -453,6 +453,37 @@ class JitterbugVecEnv:
         _lib.check(self._L.jb_score_tapes_device(self._h, int(n_steps), tapes_ptr, float(gamma), returns_ptr, alive_ptr))
         self.state_version += 1
 
+    # ---- readout: world frames, floor clearances, body velocities, momentum and energy of the whole batch (jb_readout / jb_readout_device)
+    def readout(self, frames=True, clearance=True, body_vel=False, energy=False):
+        """The current state's world poses and energies as a dict of float32 arrays, one row per env (only the outputs asked for):
+        'frames' [N, 33, 12] = [pos(3) | R(9) row major] of the ten bodies (model.BODY_NAMES order: centre of mass, rotation from the
+        orientation at qpos0), the 22 geoms (model.GEOM_NAMES order: geom centre, geom frame) and the target; 'clearance' [N, 22] signed
+        height of each geom's lowest point above the floor; 'body_vel' [N, 10, 6] world linear velocity of each centre of mass, world
+        angular velocity; 'energy' [N, 8] = [P | L about the world origin | T | V].  The pass reads the state and never writes it."""
+        n = self.num_envs
+        out = {}
+        if frames:
+            out["frames"] = np.empty((n, model.NFRAME, 12), dtype=np.float32)
+        if clearance:
+            out["clearance"] = np.empty((n, model.NGEOM), dtype=np.float32)
+        if body_vel:
+            out["body_vel"] = np.empty((n, model.NBODY, 6), dtype=np.float32)
+        if energy:
+            out["energy"] = np.empty((n, 8), dtype=np.float32)
+        _lib.check(self._L.jb_readout(self._h, _lib.ptr(out.get("frames")), _lib.ptr(out.get("clearance")), _lib.ptr(out.get("body_vel")), _lib.ptr(out.get("energy"))))
+        return out
+
+    def readout_device(self, frames_ptr=None, clearance_ptr=None, body_vel_ptr=None, energy_ptr=None, snaps_ptr=None, n_snaps=1):
+        """The same pass on device pointers (float32 [n_snaps * N, ...] each, None = absent: no stores), asynchronous.  snaps_ptr: a stack
+        of `n_snaps` device snapshots back to back (`snapshot_bytes` apart) instead of the current state; env-state k * N + j is env j of
+        snapshot k.  The result for one env-state does not depend on what else is in the launch."""
+        _lib.check(self._L.jb_readout_device(self._h, snaps_ptr, int(n_snaps), frames_ptr, clearance_ptr, body_vel_ptr, energy_ptr))
+
+    def foot_contacts(self):
+        """bool [N, 4] in model_spec.LEG_NAMES order: the foot sphere reaches below the floor (readout clearance < 0).  A foot within a few
+        nanometres of the plane may differ from the step kernel's own activation test: the two are separate roundings of the same height."""
+        return self.readout(frames=False, clearance=True)["clearance"][:, model.FOOT_GEOMS] < 0
+
     # ---- rows between GPUs through the library's own RCCL binding (jb_comm_*: no torch.distributed on the data path)
     @staticmethod
     def comm_unique_id():
