@@ -283,6 +283,41 @@ int jb_score_tapes_device(jb_handle* h, int32_t n_steps, const float* d_tapes /*
 int jb_readout_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_snaps, float* d_frames /*[n_snaps*N,33,12]*/, float* d_clearance /*[n_snaps*N,22]*/,
                       float* d_body_vel /*[n_snaps*N,10,6]*/, float* d_energy /*[n_snaps*N,8]*/);
 int jb_readout(jb_handle* h, float* frames /*[N,33,12]*/, float* clearance /*[N,22]*/, float* body_vel /*[N,10,6]*/, float* energy /*[N,8]*/);
+/* Forward dynamics (additive in ABI 5): what acts on the robot in a state.  One launch maps a state - the handle's current one, or a stack of
+ * snapshots - and an action to the accelerations the next substep would integrate and the contact forces behind them, WITHOUT advancing
+ * time.  The accelerations are those of one substep of the step kernels run on a copy of the state: the full contact solve (floor, both
+ * pair contacts, the line-searched second solve, per-env models), from the state's own warm start after the quaternion's normalisation,
+ * with the pair narrow phase started cold - exactly the first substep of a control step.  Per env-state, in fp32; vectors in MuJoCo's qvel
+ * order, as the state entry points above have it: [linear, world (3) | angular, root frame (3) | leg hinges, 6 + 2l shoulder and 7 + 2l
+ * knee of leg l | motor].  h: the timestep, b: the hinge damping, tau: -bias + springs + dampers + actuator, f: the contact forces.
+ *   qacc            [15]     y = (M + h diag(b))^-1 (tau + J^T f).  NOT MuJoCo's data.qacc where there are contacts and damping: that one
+ *                            leaves the h b term out; y is what the integrator adds to the velocity, (v1 - v0) / h of one substep.
+ *   qfrc_constraint [15]     J^T f = M y + h b o y - tau, by inverse dynamics from y.  0-2: the net floor force on the robot in world axes
+ *                            (the ground reaction; the pair contacts act between two bodies of one robot and cancel there), 3-5: the net
+ *                            contact moment about the root origin in root axes, 6-14: the contact torque on each hinge.  A difference of
+ *                            inertial terms much larger than itself: its fp32 error scales with those, not with its own size.
+ *   body_acc        [10, 6]  per body, in the readout's order: world linear acceleration of the centre of mass, then world angular
+ *                            acceleration - the time derivative of the readout's body_vel along q' = v, v' = y.  Gravity is not subtracted.
+ *   motor           [3]      [ctrl clamped to ctrlrange | joint torque gear * force | mechanical power torque * phi'], force = gain u +
+ *                            biasprm0 + biasprm1 gear (phi + 2 pi turns) + biasprm2 gear phi', as in the substep
+ *   unconverged     [1]      uint8: 1 when neither the active-set iteration nor the line-searched second solve settled - the step kernel
+ *                            would add 1 to the failure counter there
+ * The pass runs ONE lane layout for every handle: the one-wave-per-SIMD step kernel's at four envs per wave, with the pair contacts when
+ * the handle's step kernel has them.  A handle that steps with a JB_FLAG_LEAN kernel therefore gets forward results that agree with its
+ * own steps to fp32 rounding only, not bit for bit.  Nothing but the outputs is written: state, counters, solver statistics and wave
+ * clocks stay as they are.
+ *   the device form   d_snaps: n_snaps snapshots of N envs each, back to back (jb_snapshot_bytes apart), or NULL = the handle's current state
+ *                     (n_snaps must then be 1).  Env-state k * N + j is env j of snapshot k and takes env j's table.  d_ctrl [n_snaps * N]
+ *                     actions, or NULL = 0.  Each output is device memory for n_snaps * N env-states, or NULL (not all five).  The result
+ *                     for one env-state does not depend on what else is in the launch.  Asynchronous on the handle's stream.
+ *                     JB_E_INVALID, and nothing is launched: n_snaps < 1, d_snaps == NULL with n_snaps != 1, all outputs NULL, a
+ *                     jb_step_async pending.
+ *   the host form     host buffers (ctrl [N] or NULL = 0; each output nullable, not all), the current state, synchronous; the device
+ *                     staging belongs to the handle, only grows, and is freed by jb_release_staging. */
+int jb_forward_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_snaps, const float* d_ctrl /*[n_snaps*N] nullable*/, float* d_qacc /*[n_snaps*N,15]*/,
+                      float* d_qfrc /*[n_snaps*N,15]*/, float* d_body_acc /*[n_snaps*N,10,6]*/, float* d_motor /*[n_snaps*N,3]*/, uint8_t* d_unconverged /*[n_snaps*N]*/);
+int jb_forward(jb_handle* h, const float* ctrl /*[N] nullable*/, float* qacc /*[N,15]*/, float* qfrc /*[N,15]*/, float* body_acc /*[N,10,6]*/, float* motor /*[N,3]*/,
+               uint8_t* unconverged /*[N]*/);
 /* seconds each wave of the LAST step launch was alive (one wave = jb_envs_per_wave envs), out[0 .. min(n_waves, max_waves)); returns the
  * number of waves.  Mean against maximum is the load imbalance of the launch (roofline). */
 int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves);

@@ -23,6 +23,7 @@
 #include "../../include/jitterbug_hip.h"
 #include "jb_default_params.h"
 #include "jb_device_guard.hpp"
+#include "jb_forward.hpp"
 #include "jb_model_build.hpp"
 #include "jb_model_compile.hpp"
 #include "jb_nominal_spec.h"
@@ -49,6 +50,7 @@ static_assert(ROOT_F == SNAP_ROOT_F && LEG_F == SNAP_LEG_F, "jb_snapshot.hpp cop
 static_assert(RO_RF_P == RF_P && RO_RF_Q == RF_Q && RO_RF_V == RF_V && RO_RF_W == RF_W && RO_RF_PHI == RF_PHI && RO_RF_PHID == RF_PHID && RO_RF_TGT == RF_TGT && RO_RF_LO == RF_LO &&
               RO_LF_TH1 == LF_TH1 && RO_LF_TH2 == LF_TH2 && RO_LF_THD1 == LF_THD1 && RO_LF_THD2 == LF_THD2, "jb_readout.hpp reads exactly the state fields declared here");
 static_assert(RO_NFRAME == JB_NFRAME, "the header promises this many frames");
+static_assert(FW_RF_TURNS == RF_TURNS && FW_RF_WA == RF_WA && FW_RF_WL == RF_WL && FW_RF_WM == RF_WM && FW_LF_WJ0 == LF_WJ0 && FW_LF_WJ1 == LF_WJ1, "jb_forward.hpp names exactly the state fields declared here");
 
 struct KArgs {
     int n, task, substeps, step_limit, auto_reset, contacts, max_newton, random_pose, per_env_model;
@@ -448,6 +450,104 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     step_body<EPW, true, true>(a, io);
 }
 
+// ---------------------------------------------------------------------------------------------- forward dynamics (jb_forward.hpp)
+// One substep on a COPY of a state, then inverse dynamics on (state, y): accelerations and contact forces without advancing time.  The wave is
+// the step kernels' at four envs per wave, one wave per SIMD - step_layout(4, false, PAIR): the same scratch binding, helper / replica / aux
+// lane groups, table staging, SC_ZERO initialisation and options as step_body, so the substep runs exactly the instruction stream of that
+// step kernel's first substep of a control step.  One layout serves every handle (the pass is off the hot path); PAIR follows the handle's
+// KArgs::pair.  A handle that STEPS with a LEAN kernel therefore gets forward results that agree with its own steps to fp32 rounding only
+// (the two instantiations fuse multiply-adds differently: see jb_step_kernel_lean above).
+// Workgroup b = wave b % waves_per_snap of snapshot b / waves_per_snap: a wave never straddles two snapshots, so stage_model works unchanged.
+// A quad past the end of a snapshot repeats its last env (loads stay inside the blocks, every quad of the wave stays complete for the quad
+// and wave operations; its rows are never copied out).  The main lanes then reload the untouched input state, run fw_lane and write their rows
+// into an LDS image of the block's part of each output array (the scratch is dead by then); the wave copies each present image out as one
+// contiguous segment, in 16-byte words where the segment starts on one.  Nothing but the outputs is written.
+struct FwArgs {
+    SnapView first;              // snapshot 0 (or the handle's blocks)
+    long long stride_words;      // distance between consecutive snapshots, in 4-byte words
+    int waves_per_snap;          // ceil(N / 4)
+    const float* ctrl;           // nullable [n_snaps * N]: the action of every env-state (NULL: 0)
+    float *qacc, *qfrc, *bacc, *motor; unsigned char* unconv;      // each nullable
+};
+constexpr int FW_EPW = 4;
+constexpr int FW_LDS_QACC = 0, FW_LDS_QFRC = FW_LDS_QACC + FW_EPW * FW_NV, FW_LDS_BACC = FW_LDS_QFRC + FW_EPW * FW_NV, FW_LDS_MOTOR = FW_LDS_BACC + FW_EPW * FW_BACC,
+              FW_LDS_FLOATS = FW_LDS_MOTOR + FW_EPW * FW_MOTOR;
+static_assert(FW_LDS_QFRC % 4 == 0 && FW_LDS_BACC % 4 == 0 && FW_LDS_MOTOR % 4 == 0, "every LDS image starts on a 16-byte word");
+static_assert(FW_LDS_FLOATS <= SC_COUNT * 4 * FW_EPW, "the images fit into the (dead) scratch");
+template <bool PAIR>
+__global__ __launch_bounds__(64) void jb_forward_kernel(KArgs a, FwArgs f) {
+    extern __shared__ float lds[];           // [SC_COUNT][16] per-lane scratch, then the lane constant table(s): step_body's layout
+    constexpr StepLayout LAY = step_layout(FW_EPW, false, PAIR);
+    constexpr int MAIN = LAY.main_lanes, SCN = LAY.scratch_floats;
+    static_assert(LAY.groups * MAIN == 64 && LAY.offload && LAY.red_lds && !LAY.split_tables && LAY.ovc_floats == 0, "the one-wave-per-SIMD layout at four envs per wave fills the wave");
+    const int lane_in_grp = threadIdx.x % MAIN, grp = threadIdx.x / MAIN, quad = lane_in_grp >> 2, leg = threadIdx.x & 3;
+    const int k = (int)blockIdx.x / f.waves_per_snap, lblock = (int)blockIdx.x - k * f.waves_per_snap;
+    LaneModel<float> m;
+    stage_model<false>(a, lds + SCN * MAIN, lblock, quad, leg, m, false, LAY.pair_entries, LAY.aux ? grp : -1);      // (a.epw == FW_EPW: jb_forward_device)
+    int env = lblock * FW_EPW + quad;
+    if (env >= a.n) env = a.n - 1;
+    LaneScratch<float> scr;
+    scr.p = lds + lane_in_grp;
+    scr.stride = MAIN;
+    scr.grp = grp; scr.ngrp = LAY.groups; scr.gstride = MAIN;
+    scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds;
+    scr.ovc_stride = MAIN;
+    scr.pd = LAY.pd;
+    scr.aux_lane = LAY.aux && grp >= 2;
+    SnapView v = f.first;
+    v.root += (long long)k * f.stride_words; v.leg += (long long)k * f.stride_words;
+    const bool rep = holds_state(LAY, grp);
+    LaneState<float> s;
+    if (rep) {
+        KArgs av;                 // the fields load_state reads
+        av.n = a.n; av.root = (float*)v.root; av.leg = (float*)v.leg;
+        load_state(av, env, env * 4 + leg, s);
+    } else helper_lane_state(s);
+    s.fail = 0.f;                 // counts this substep alone
+#ifdef JB_WAVE_STATS
+    s.st_xtra = 0.f; s.st_sweeps = 0.f; s.st_contact = 0.f; s.st_slots = 0.f; s.st_fast = 0.f; s.st_checks = 0.f;
+#endif
+    const SimOpts o = sim_opts(LAY, a.contacts, a.max_newton, 1, a.rank_one, a.spread);
+    if (grp == 0) {
+#pragma unroll
+        for (int i = 0; i < 56; i++) scr.st(SC_ZERO + i, 0.f);
+    }
+    float ctrl = 0.f;
+    if (rep && f.ctrl) ctrl = f.ctrl[(size_t)k * a.n + env];
+    if (rep) normalise_state(s);
+    if (PAIR && rep) scr.st(scr.pd + 11, 0.f);      // the narrow phase starts cold, as in the first substep of a control step
+    (void)substep<float, PAIR>(m, scr, s, ctrl, o);
+    __syncthreads();                                // every lane group is done with the scratch: it becomes the output images
+    if (grp == 0) {
+        const FwState<float> st = fw_load<float>(v, env, leg);
+        FwAcc<float> y;
+#pragma unroll
+        for (int i = 0; i < 3; i++) { y.lin[i] = s.wl[i]; y.ang[i] = s.wa[i]; }
+        y.j1 = s.wj[0]; y.j2 = s.wj[1]; y.m = s.wm;
+        FwOut<float> out;
+        out.qacc = f.qacc ? lds + FW_LDS_QACC + quad * FW_NV : nullptr;
+        out.qfrc = f.qfrc ? lds + FW_LDS_QFRC + quad * FW_NV : nullptr;
+        out.bacc = f.bacc ? lds + FW_LDS_BACC + quad * FW_BACC : nullptr;
+        out.motor = f.motor ? lds + FW_LDS_MOTOR + quad * FW_MOTOR : nullptr;
+        float p[6];
+        fw_lane<float>(st, y, ctrl, m.c.inv, leg, out, p);
+        if (out.qfrc) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) { const float t = quad_sum(p[i]); if (leg == (i & 3)) out.qfrc[i] = t; }
+        }
+        if (f.unconv && leg == 0 && lblock * FW_EPW + quad < a.n) f.unconv[(size_t)k * a.n + env] = s.fail > 0.f ? 1 : 0;
+    }
+    __syncthreads();
+    const int left = a.n - lblock * FW_EPW, n_es = left < FW_EPW ? left : FW_EPW, tid = threadIdx.x;
+    const size_t es0 = (size_t)k * a.n + (size_t)lblock * FW_EPW;
+    auto store = [&](float* arr, int at, int len) {
+        if (!arr) return;
+        float* dst = arr + es0 * len;
+        ro_store_segment(dst, lds + at, n_es * len, (((uintptr_t)dst) & 15u) == 0 ? 1 : 0, tid);
+    };
+    store(f.qacc, FW_LDS_QACC, FW_NV); store(f.qfrc, FW_LDS_QFRC, FW_NV); store(f.bacc, FW_LDS_BACC, FW_BACC); store(f.motor, FW_LDS_MOTOR, FW_MOTOR);
+}
+
 // Self-check of the kernarg-segment reads above, run once per process before the first handle is handed out: a kernel with the step kernels'
 // argument list compares what it reads through kernarg_base() with the arguments it received by value.
 __global__ void jb_kernarg_probe_kernel(KArgs a, StepIO io, int* ok) {
@@ -753,6 +853,7 @@ struct jb_handle {
     Dev<float> d_tape, d_rows_stage, d_rew_stage;      // staging of the host-buffer rollouts (jb_step_many, jb_rollout_policy): grow-only
     Dev<unsigned char> d_done_stage;                   // jb_score_tapes_device: the done flags of every step, next to d_rew_stage (grow-only)
     Dev<float> d_readout_stage;                        // jb_readout: the outputs on their way to the host (grow-only)
+    Dev<float> d_forward_stage;                        // jb_forward: the actions on their way in, the outputs on their way out (grow-only)
     Dev<uint32_t> d_snap_stage; Dev<int> d_src_stage;  // jb_snapshot / jb_restore: the raw blocks and the index map on their way to / from the host (grow-only)
     Dev<int> d_wave_order;           // launch order of the waves (jb_wave_order_kernel), empty while the device holds the whole batch at once
     int wave_slots;                  // waves the device holds at once with this handle's kernel variant
@@ -885,6 +986,17 @@ template <int I> static StepKernel step_row_kernel() {
 template <int... I> static const StepKernel* step_kernels(std::integer_sequence<int, I...>) {
     static const StepKernel table[] = {step_row_kernel<I>()...};      // by row of STEP_ROWS
     return table;
+}
+// ... and the forward pass of a handle (jb_forward_kernel), by whether its step kernel has the pair contacts
+typedef void (*ForwardKernel)(KArgs, FwArgs);
+template <bool PAIR> static ForwardKernel forward_kernel() {
+#ifdef JB_DEV_ONLY4      // development builds: the ordinary layout only, like the step kernels
+    constexpr bool built = !PAIR;
+#else
+    constexpr bool built = true;
+#endif
+    if constexpr (!built) return nullptr;
+    else return jb_forward_kernel<PAIR>;
 }
 static int kernel_variant(const KArgs& k) { return step_variant(k.lean, k.pair, k.per_env_model, k.epw); }
 static int check_variant(int lean, int pair, int per_env_model, int epw) {
@@ -1284,7 +1396,7 @@ int jb_release_staging(jb_handle* h) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
     h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset(); h->d_done_stage.reset();
-    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset();
+    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset(); h->d_forward_stage.reset();
     return JB_OK;
 }
 // ---------------------------------------------------------------------------------------------- snapshot / restore / fork, tape scoring
@@ -1431,6 +1543,56 @@ int jb_readout(jb_handle* h, float* frames, float* clearance, float* body_vel, f
     if (clearance) JB_HIP(hipMemcpyAsync(clearance, d_cl, sizeof(float) * N * RO_CLEAR, hipMemcpyDeviceToHost, h->stream));
     if (body_vel) JB_HIP(hipMemcpyAsync(body_vel, d_bv, sizeof(float) * N * RO_BVEL, hipMemcpyDeviceToHost, h->stream));
     if (energy) JB_HIP(hipMemcpyAsync(energy, d_en, sizeof(float) * N * RO_ENERGY, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipStreamSynchronize(h->stream));
+    return JB_OK;
+}
+// The forward-dynamics pass (jb_forward_kernel above): one launch over n_snaps * ceil(N / 4) waves; reads the state, writes only its outputs.
+int jb_forward_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, const float* d_ctrl, float* d_qacc, float* d_qfrc, float* d_body_acc, float* d_motor, uint8_t* d_unconverged) {
+    JB_ENTER(h);
+    if (n_snaps < 1) return fail(JB_E_INVALID, "jb_forward_device: n_snaps must be >= 1");
+    if (!d_qacc && !d_qfrc && !d_body_acc && !d_motor && !d_unconverged) return fail(JB_E_INVALID, "jb_forward_device: all five outputs are NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_forward_device: a jb_step_async is pending (jb_step_wait first)");
+    if (!d_snaps && n_snaps != 1) return fail(JB_E_INVALID, "jb_forward_device: the handle's current state is ONE state (n_snaps must be 1 without a snapshot stack)");
+    const ForwardKernel kernel = h->ka.pair ? forward_kernel<true>() : forward_kernel<false>();
+    if (!kernel) return fail(JB_E_INVALID, "JB_DEV_ONLY4 build: only the forward pass without the pair contacts");
+    RoctxRange range("jb_forward");
+    const int N = h->cfg.n_envs;
+    const StepLayout lay = step_layout(FW_EPW, false, h->ka.pair != 0);
+    KArgs a = h->ka;
+    a.epw = FW_EPW; a.lean = 0;      // the pass has its own layout, whichever kernel the handle steps with
+    FwArgs f;
+    f.first = d_snaps ? snap_view(const_cast<void*>(d_snaps), N) : state_view(h);      // (const_cast: the pass only reads)
+    f.stride_words = (long long)SNAP_WORDS * N;
+    f.waves_per_snap = (N + FW_EPW - 1) / FW_EPW;
+    f.ctrl = d_ctrl;
+    f.qacc = d_qacc; f.qfrc = d_qfrc; f.bacc = d_body_acc; f.motor = d_motor; f.unconv = d_unconverged;
+    const long long blocks = (long long)n_snaps * f.waves_per_snap;
+    if (blocks > 0x7fffffffLL) return fail(JB_E_INVALID, "jb_forward_device: too many env-states for one launch");
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), step_lds_bytes(lay, h->ka.per_env_model != 0), h->stream, a, f);
+    JB_HIP(hipGetLastError());
+    return JB_OK;
+}
+int jb_forward(jb_handle* h, const float* ctrl, float* qacc, float* qfrc, float* body_acc, float* motor, uint8_t* unconverged) {
+    JB_ENTER(h);
+    if (!qacc && !qfrc && !body_acc && !motor && !unconverged) return fail(JB_E_INVALID, "jb_forward: all five outputs are NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_forward: a jb_step_async is pending (jb_step_wait first)");
+    const size_t N = (size_t)h->cfg.n_envs;
+    int rc = grow_stage(h, h->d_forward_stage, N * (size_t)(FW_BACC + 2 * FW_NV + FW_MOTOR + 1) + (N + 3) / 4, "the forward pass");
+    if (rc) return rc;
+    float* d_ba = h->d_forward_stage.get();
+    float* d_qa = d_ba + N * FW_BACC;
+    float* d_qf = d_qa + N * FW_NV;
+    float* d_mo = d_qf + N * FW_NV;
+    float* d_u = d_mo + N * FW_MOTOR;
+    uint8_t* d_un = (uint8_t*)(d_u + N);
+    if (ctrl) JB_HIP(hipMemcpyAsync(d_u, ctrl, sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
+    rc = jb_forward_device(h, nullptr, 1, ctrl ? d_u : nullptr, qacc ? d_qa : nullptr, qfrc ? d_qf : nullptr, body_acc ? d_ba : nullptr, motor ? d_mo : nullptr, unconverged ? d_un : nullptr);
+    if (rc) return rc;
+    if (qacc) JB_HIP(hipMemcpyAsync(qacc, d_qa, sizeof(float) * N * FW_NV, hipMemcpyDeviceToHost, h->stream));
+    if (qfrc) JB_HIP(hipMemcpyAsync(qfrc, d_qf, sizeof(float) * N * FW_NV, hipMemcpyDeviceToHost, h->stream));
+    if (body_acc) JB_HIP(hipMemcpyAsync(body_acc, d_ba, sizeof(float) * N * FW_BACC, hipMemcpyDeviceToHost, h->stream));
+    if (motor) JB_HIP(hipMemcpyAsync(motor, d_mo, sizeof(float) * N * FW_MOTOR, hipMemcpyDeviceToHost, h->stream));
+    if (unconverged) JB_HIP(hipMemcpyAsync(unconverged, d_un, N, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }

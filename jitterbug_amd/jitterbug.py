@@ -123,6 +123,15 @@ class Physics:
             self._frames_version = self._venv.state_version
         return self._frames_cache
 
+    def forward(self, action=0.0):
+        """mj_forward for this env under `action`, without advancing time: a dict with 'qacc' [15] (the acceleration the next substep
+        integrates) and 'qfrc_constraint' [15] (the contact forces in joint space; 0-2: the ground reaction in world axes), float32 in qvel
+        order (JitterbugVecEnv.forward; the other envs of the batch are evaluated with action 0)."""
+        a = np.zeros(self._venv.num_envs, dtype=np.float32)
+        a[self._i] = float(np.asarray(action, dtype=np.float64).reshape(-1)[0])
+        out = self._venv.forward(a, qacc=True, qfrc=True)
+        return {"qacc": out["qacc"][self._i].copy(), "qfrc_constraint": out["qfrc_constraint"][self._i].copy()}
+
     @property
     def _params(self):
         return self._venv.model_params(self._i)

@@ -14,10 +14,11 @@ from . import model
 class Trajectory:
     """frames [K+1, N, 33, 12] and clearance [K+1, N, 22] (float32 torch device tensors; rows as JitterbugVecEnv.readout gives them),
     snapshots [K+1, snapshot_bytes] (uint8: the stack itself - restore_device row k to continue from step k) and the packed rows
-    [K, N, D+2] = [obs | reward | done] of the steps."""
+    [K, N, D+2] = [obs | reward | done] of the steps.  qfrc [K, N, 15] (record(..., forces=True), else None): the contact forces in joint
+    space at the state BEFORE step k under action k, as JitterbugVecEnv.forward gives them (0-2: the ground reaction in world axes)."""
 
-    def __init__(self, frames, clearance, snapshots, rows, params):
-        self.frames, self.clearance, self.snapshots, self.rows = frames, clearance, snapshots, rows
+    def __init__(self, frames, clearance, snapshots, rows, params, qfrc=None):
+        self.frames, self.clearance, self.snapshots, self.rows, self.qfrc = frames, clearance, snapshots, rows, qfrc
         self._params = params          # env index -> float64[NPARAM] table that env was simulated with
 
     @property
@@ -27,24 +28,29 @@ class Trajectory:
     def save_npz(self, path, envs):
         """Write envs `envs` (a list of indices): frames [K+1, E, 33, 12], clearance [K+1, E, 22], geom_type [E, 22]
         (0 sphere, 1 cylinder, 2 box, 3 ellipsoid) and geom_size [E, 22, 3] from the envs' model tables, frame_names [33], geom_names [22],
-        body_names [10], envs [E]."""
+        body_names [10], envs [E]; with recorded forces also qfrc [K, E, 15]."""
         envs = [int(e) for e in envs]
         P = np.stack([np.asarray(self._params(e), dtype=np.float64) for e in envs])
         g = P[:, model.P_GEOM:model.P_GEOM + model.NGEOM * model.GEOM_STRIDE].reshape(len(envs), model.NGEOM, model.GEOM_STRIDE)
         idx = self.frames.new_tensor(envs).long()
+        extra = {} if self.qfrc is None else dict(qfrc=self.qfrc.index_select(1, idx).cpu().numpy())
         np.savez(path, frames=self.frames.index_select(1, idx).cpu().numpy(), clearance=self.clearance.index_select(1, idx).cpu().numpy(),
                  geom_type=g[:, :, model.G_TYPE].astype(np.int32), geom_size=g[:, :, model.G_SIZE:model.G_SIZE + 3].copy(),
                  frame_names=np.array(model.BODY_NAMES + model.GEOM_NAMES + ("target",)), geom_names=np.array(model.GEOM_NAMES),
-                 body_names=np.array(model.BODY_NAMES), envs=np.array(envs, dtype=np.int64))
+                 body_names=np.array(model.BODY_NAMES), envs=np.array(envs, dtype=np.int64), **extra)
 
 
-def record(venv, n_steps, actions=None):
+def record(venv, n_steps, actions=None, forces=False):
     """Step `venv` n_steps times - with the action tape `actions` [n_steps, N], or with the task's heuristic policy evaluated in the step
     kernel when None - and return the Trajectory.  The steps are the ordinary single-step launches: the env ends in the state, and with
-    the rows, n_steps calls of step would have produced; snapshots and the readout only read."""
+    the rows, n_steps calls of step would have produced; snapshots and the readout only read.  forces=True (needs the action tape): ONE
+    forward pass (JitterbugVecEnv.forward_device) over snapshots 0 .. K-1 with the tape keeps qfrc [K, N, 15] - row k is what a live forward
+    before step k with action k would have given, bit for bit."""
     import torch
     K, N = int(n_steps), venv.num_envs
     assert K >= 0
+    if forces and actions is None:
+        raise ValueError("record(forces=True) needs the action tape: the heuristic policy's actions stay inside the step kernel")
     dev = torch.device("cuda", int(venv.cfg.device_id))
     cur = torch.cuda.current_stream(dev)
     env_stream = torch.cuda.ExternalStream(int(venv.stream), device=dev) if venv.stream else torch.cuda.default_stream(dev)
@@ -62,6 +68,11 @@ def record(venv, n_steps, actions=None):
         venv.step_many_device(1, None if tape is None else tape[k].data_ptr(), rows[k].data_ptr())
         venv.snapshot_device(snaps[k + 1].data_ptr())
     venv.readout_device(frames.data_ptr(), clearance.data_ptr(), snaps_ptr=snaps.data_ptr(), n_snaps=K + 1)
+    qfrc = None
+    if forces:
+        qfrc = torch.empty((K, N, model.NV), dtype=torch.float32, device=dev)
+        if K > 0:
+            venv.forward_device(tape.data_ptr(), qfrc_ptr=qfrc.data_ptr(), snaps_ptr=snaps.data_ptr(), n_snaps=K)
     cur.wait_stream(env_stream)
     venv.synchronize()
-    return Trajectory(frames, clearance, snaps, rows, venv.model_params)
+    return Trajectory(frames, clearance, snaps, rows, venv.model_params, qfrc)

@@ -484,6 +484,43 @@ class JitterbugVecEnv:
         nanometres of the plane may differ from the step kernel's own activation test: the two are separate roundings of the same height."""
         return self.readout(frames=False, clearance=True)["clearance"][:, model.FOOT_GEOMS] < 0
 
+    # ---- forward dynamics: accelerations and contact forces at the current state, without advancing time (jb_forward / jb_forward_device)
+    def forward(self, actions=None, qacc=True, qfrc=True, body_acc=False, motor=False):
+        """What acts on the robots in the current state under `actions` (None: 0), as a dict of arrays, one row per env (only the outputs
+        asked for, and always 'unconverged'); vectors in qvel order [linear, world | angular, root frame | leg hinges | motor]:
+        'qacc' [N, 15] the acceleration the next substep would integrate - the step kernel's own contact solve, run on a copy of the state;
+        'qfrc_constraint' [N, 15] the contact forces in joint space (0-2: the net floor force on the robot in world axes, 3-5: the contact
+        moment about the root origin in root axes, 6-14: the contact torque on each hinge); 'body_acc' [N, 10, 6] world linear acceleration
+        of each body's centre of mass and its world angular acceleration (model.BODY_NAMES order; gravity not subtracted); 'motor' [N, 3] =
+        [clamped ctrl | joint torque | mechanical power]; 'unconverged' [N] bool: the contact solve did not settle.  The state, the counters
+        and the solver statistics are left as they are."""
+        n = self.num_envs
+        a = None if actions is None else np.ascontiguousarray(np.broadcast_to(np.asarray(actions, dtype=np.float32).reshape(-1), (n,)))
+        out = {}
+        if qacc:
+            out["qacc"] = np.empty((n, model.NV), dtype=np.float32)
+        if qfrc:
+            out["qfrc_constraint"] = np.empty((n, model.NV), dtype=np.float32)
+        if body_acc:
+            out["body_acc"] = np.empty((n, model.NBODY, 6), dtype=np.float32)
+        if motor:
+            out["motor"] = np.empty((n, 3), dtype=np.float32)
+        unc = np.empty(n, dtype=np.uint8)
+        _lib.check(self._L.jb_forward(self._h, _lib.ptr(a), _lib.ptr(out.get("qacc")), _lib.ptr(out.get("qfrc_constraint")), _lib.ptr(out.get("body_acc")),
+                                      _lib.ptr(out.get("motor")), _lib.ptr(unc)))
+        out["unconverged"] = unc.view(np.bool_)
+        return out
+
+    def forward_device(self, ctrl_ptr=None, qacc_ptr=None, qfrc_ptr=None, body_acc_ptr=None, motor_ptr=None, unconverged_ptr=None, snaps_ptr=None, n_snaps=1):
+        """The same pass on device pointers (float32 [n_snaps * N, ...] each, unconverged uint8; None = absent: no stores; ctrl None = 0),
+        asynchronous.  snaps_ptr: a stack of `n_snaps` device snapshots back to back (`snapshot_bytes` apart) instead of the current state;
+        env-state k * N + j is env j of snapshot k.  The result for one env-state does not depend on what else is in the launch."""
+        _lib.check(self._L.jb_forward_device(self._h, snaps_ptr, int(n_snaps), ctrl_ptr, qacc_ptr, qfrc_ptr, body_acc_ptr, motor_ptr, unconverged_ptr))
+
+    def ground_reaction(self, actions=None):
+        """float32 [N, 3]: the net force of the floor on each robot in world axes, newtons (rows 0-2 of forward()'s 'qfrc_constraint')."""
+        return self.forward(actions, qacc=False, qfrc=True)["qfrc_constraint"][:, 0:3].copy()
+
     # ---- rows between GPUs through the library's own RCCL binding (jb_comm_*: no torch.distributed on the data path)
     @staticmethod
     def comm_unique_id():
