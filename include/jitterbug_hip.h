@@ -318,6 +318,43 @@ int jb_forward_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_
                       float* d_qfrc /*[n_snaps*N,15]*/, float* d_body_acc /*[n_snaps*N,10,6]*/, float* d_motor /*[n_snaps*N,3]*/, uint8_t* d_unconverged /*[n_snaps*N]*/);
 int jb_forward(jb_handle* h, const float* ctrl /*[N] nullable*/, float* qacc /*[N,15]*/, float* qfrc /*[N,15]*/, float* body_acc /*[N,10,6]*/, float* motor /*[N,3]*/,
                uint8_t* unconverged /*[N]*/);
+/* Contacts (additive in ABI 5): which contacts a state has and what force each one carries - MuJoCo's data.contact and mj_contactForce on a
+ * pyramidal cone.  One launch maps a state and an action to them WITHOUT advancing time.  The contacts are those the first substep of a
+ * control step detects and solves: the floor against all 22 geoms and, where the handle's step kernel has the pair contacts, each upper-leg
+ * cylinder against the motor-axis thread and the eccentric mass.  Action, warm start, quaternion normalisation and the cold pair narrow
+ * phase are jb_forward's, so the accelerations behind the forces are jb_forward's qacc bit for bit.
+ *   A contact is one candidate slot of the step kernels' collision phase; the slot table is fixed: JB_NCONTACT rows, row r always the same
+ *   pair of geoms - jb_contact_slot_geoms writes (geom1, geom2) of every row, geoms in the parameter table's order, geom1 = -1 for the
+ *   floor; a pair row's geom1 is the leg's cylinder, its geom2 the thread (20) or the mass (21).  Several rows share a geom (a cylinder
+ *   touches the floor in up to four points, a box in up to four of its eight vertices).
+ *   contact   [JB_NCONTACT, 12]  fp32 [pos(3) | normal(3) | force(3) | dist | fn | active], world axes.  pos: the point between the two
+ *                                surfaces.  normal: unit, from geom1 to geom2 (+z for the floor).  dist: signed distance, negative when
+ *                                penetrating.  fn: the sum of the four edge forces, >= 0.  force = fn n + mu (f0 - f1) t1 + mu (f2 - f3) t2:
+ *                                the force on geom2, geom1 receives the opposite; edges J_n +- mu J_t1, J_n +- mu J_t2 with
+ *                                mu = friction sqrt(1 / impratio), f_e = D max(0, -(J_e y - aref_e)) at the solve's y.  active: 1 or 0;
+ *                                an inactive row is all zeros.
+ *   ncon      [1]                int32: the number of active rows
+ *   geom_frc  [22, 3]            per geom, the world force the floor exerts on it (the sum over its floor rows; pair contacts act inside
+ *                                the robot and are not in it).  Its sum over the geoms equals jb_forward's qfrc_constraint[0:3] up to the
+ *                                fp32 rounding of the two computations (a sum of edge forces here, inverse dynamics there).
+ *   unconverged [1]              uint8, as jb_forward's
+ * Lane layout, the JB_FLAG_LEAN caveat (agreement with the handle's own steps to fp32 rounding only), the device and the host form, the
+ * argument rules and the JB_E_INVALID cases are jb_forward's (all outputs NULL: all four).  Nothing but the outputs is written.
+ * What an env-state's result depends on: never on its snapshot's place in the stack, on the other snapshots, or on which outputs are
+ * present.  On the other envs of its wave (the four env-states of a workgroup) exactly where the substep underneath does: a wave whose
+ * envs hold many contacts sweeps its leg slots in spread mode, a wave with few does not, and for some states the two orders of summation
+ * round differently - measured 3e-7 relative in qacc and in the forces, between a batch of five and the state alone.  jb_forward shares
+ * that substep and that caveat.  A handle created with JB_FLAG_NO_SPREAD has no spread sweeps: there an env-state's result does not
+ * depend on what else is in the launch, bit for bit. */
+#define JB_NCONTACT 74
+#define JB_CONTACT_WIDTH 12
+int32_t jb_contact_rows(void);                 /* JB_NCONTACT of the library that is loaded */
+void jb_contact_slot_geoms(int32_t* out /*[JB_NCONTACT,2]*/);
+int jb_contacts_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_snaps, const float* d_ctrl /*[n_snaps*N] nullable*/,
+                       float* d_contact /*[n_snaps*N,JB_NCONTACT,12]*/, int32_t* d_ncon /*[n_snaps*N]*/, float* d_geom_frc /*[n_snaps*N,22,3]*/,
+                       uint8_t* d_unconverged /*[n_snaps*N]*/);
+int jb_contacts(jb_handle* h, const float* ctrl /*[N] nullable*/, float* contact /*[N,JB_NCONTACT,12]*/, int32_t* ncon /*[N]*/, float* geom_frc /*[N,22,3]*/,
+                uint8_t* unconverged /*[N]*/);
 /* seconds each wave of the LAST step launch was alive (one wave = jb_envs_per_wave envs), out[0 .. min(n_waves, max_waves)); returns the
  * number of waves.  Mean against maximum is the load imbalance of the launch (roofline). */
 int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves);

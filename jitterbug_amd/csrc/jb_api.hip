@@ -24,6 +24,7 @@
 #include "jb_default_params.h"
 #include "jb_device_guard.hpp"
 #include "jb_forward.hpp"
+#include "jb_contacts.hpp"
 #include "jb_model_build.hpp"
 #include "jb_model_compile.hpp"
 #include "jb_nominal_spec.h"
@@ -548,6 +549,114 @@ __global__ __launch_bounds__(64) void jb_forward_kernel(KArgs a, FwArgs f) {
     store(f.qacc, FW_LDS_QACC, FW_NV); store(f.qfrc, FW_LDS_QFRC, FW_NV); store(f.bacc, FW_LDS_BACC, FW_BACC); store(f.motor, FW_LDS_MOTOR, FW_MOTOR);
 }
 
+// ---------------------------------------------------------------------------------------------- contacts (jb_contacts.hpp)
+// The forward pass's wave, launch shape and substep - step_layout(4, false, PAIR), n_snaps x ceil(N / 4) workgroups, a ragged last quad
+// repeats its last env - so the solve behind the forces is the one behind jb_forward_kernel's qacc, bit for bit.  The substep is handed a
+// SolveTap: the scratch entries it leaves are packed by rank among the wave's live slots.  The scratch is NOT dead afterwards - the rows are read from it - so the
+// output images have LDS of their own behind the constant tables (CtArgs::img: 15 KB; 51 KB per wave with one model per env).  They are
+// zeroed before the substep; the main lanes then walk the live slots (a wave-uniform loop), every lane evaluates the slot for its leg
+// (ct_slot) and a lane that can hold a contact there writes its row, adds a floor row's force to its geom's three words - every geom belongs
+// to one lane, no exchange - and counts.  The wave copies each present image out as one contiguous segment.  Nothing but the outputs is written.
+struct CtArgs {
+    SnapView first;              // snapshot 0 (or the handle's blocks)
+    long long stride_words;      // distance between consecutive snapshots, in 4-byte words
+    int waves_per_snap;          // ceil(N / 4)
+    int img;                     // where the images start in the dynamic LDS, in floats (a multiple of 4: behind the scratch and the tables)
+    const float* ctrl;           // nullable [n_snaps * N]
+    float *contact, *geom_frc; int* ncon; unsigned char* unconv;      // each nullable
+};
+constexpr int CT_LDS_TABLE = 0, CT_LDS_GEOM = CT_LDS_TABLE + FW_EPW * CT_TABLE, CT_LDS_FLOATS = CT_LDS_GEOM + FW_EPW * CT_GEOMF;
+static_assert(CT_LDS_GEOM % 4 == 0 && CT_LDS_FLOATS % 4 == 0 && CT_TABLE % 4 == 0 && (FW_EPW * CT_GEOMF) % 4 == 0, "every LDS image starts on a 16-byte word and a full block's segment is whole words");
+template <bool PAIR>
+__global__ __launch_bounds__(64) void jb_contacts_kernel(KArgs a, CtArgs f) {
+    extern __shared__ float lds[];           // [SC_COUNT][16] per-lane scratch, the lane constant table(s), then the output images
+    constexpr StepLayout LAY = step_layout(FW_EPW, false, PAIR);
+    constexpr int MAIN = LAY.main_lanes, SCN = LAY.scratch_floats;
+    static_assert(LAY.groups * MAIN == 64 && LAY.offload && LAY.red_lds && !LAY.split_tables && LAY.ovc_floats == 0, "the one-wave-per-SIMD layout at four envs per wave fills the wave");
+    const int lane_in_grp = threadIdx.x % MAIN, grp = threadIdx.x / MAIN, quad = lane_in_grp >> 2, leg = threadIdx.x & 3, tid = threadIdx.x;
+    const int k = (int)blockIdx.x / f.waves_per_snap, lblock = (int)blockIdx.x - k * f.waves_per_snap;
+    float* const img = lds + f.img;
+    for (int i = tid; i < CT_LDS_FLOATS / 4; i += 64) ((float4*)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);      // an inactive row is all zeros
+    LaneModel<float> m;
+    stage_model<false>(a, lds + SCN * MAIN, lblock, quad, leg, m, false, LAY.pair_entries, LAY.aux ? grp : -1);      // (a.epw == FW_EPW: jb_contacts_device)
+    int env = lblock * FW_EPW + quad;
+    if (env >= a.n) env = a.n - 1;
+    LaneScratch<float> scr;
+    scr.p = lds + lane_in_grp;
+    scr.stride = MAIN;
+    scr.grp = grp; scr.ngrp = LAY.groups; scr.gstride = MAIN;
+    scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds;
+    scr.ovc_stride = MAIN;
+    scr.pd = LAY.pd;
+    scr.aux_lane = LAY.aux && grp >= 2;
+    SnapView v = f.first;
+    v.root += (long long)k * f.stride_words; v.leg += (long long)k * f.stride_words;
+    const bool rep = holds_state(LAY, grp);
+    LaneState<float> s;
+    if (rep) {
+        KArgs av;                 // the fields load_state reads
+        av.n = a.n; av.root = (float*)v.root; av.leg = (float*)v.leg;
+        load_state(av, env, env * 4 + leg, s);
+    } else helper_lane_state(s);
+    s.fail = 0.f;                 // counts this substep alone
+#ifdef JB_WAVE_STATS
+    s.st_xtra = 0.f; s.st_sweeps = 0.f; s.st_contact = 0.f; s.st_slots = 0.f; s.st_fast = 0.f; s.st_checks = 0.f;
+#endif
+    const SimOpts o = sim_opts(LAY, a.contacts, a.max_newton, 1, a.rank_one, a.spread);
+    if (grp == 0) {
+#pragma unroll
+        for (int i = 0; i < 56; i++) scr.st(SC_ZERO + i, 0.f);
+    }
+    float ctrl = 0.f;
+    if (rep && f.ctrl) ctrl = f.ctrl[(size_t)k * a.n + env];
+    if (rep) normalise_state(s);
+    if (PAIR && rep) scr.st(scr.pd + 11, 0.f);      // the narrow phase starts cold, as in the first substep of a control step
+    CtTap<float> tap;
+    (void)substep<float, PAIR, SolveTap<float>>(m, scr, s, ctrl, o, tap.tap());
+    const unsigned live = tap.live;
+    __syncthreads();                                // the solve's last scratch writes, and the zeroed images
+    if (grp == 0) {
+        const RoState<float> st = ro_load<float>(v, env, leg);
+        CtPose<float> P;
+        P.R = ro_quat2mat(st.q, st.ql); P.px = st.px; P.py = st.py; P.pz = st.pz; P.pz_lo = st.pz_lo;
+        const CtY<float> y = ct_y<float>(scr, tap);
+        float* const rows = f.contact ? img + CT_LDS_TABLE + quad * CT_TABLE : nullptr;
+        float* const gfrc = f.geom_frc ? img + CT_LDS_GEOM + quad * CT_GEOMF : nullptr;
+        unsigned count = 0u;
+#pragma unroll 1
+        for (unsigned rest = live; rest; rest &= rest - 1u) {
+            const int slot = __builtin_ctz(rest);
+            CtRowOut<float> r;
+            ct_slot<float, PAIR>(m, scr, live, slot, P, y, r);
+            if (ct_has_row(leg, slot)) {
+                if (rows) {
+                    float* q = rows + ct_row(leg, slot) * CT_W;
+#pragma unroll
+                    for (int i = 0; i < CT_W; i++) q[i] = r.v[i];
+                }
+                if (gfrc && slot < SLOT_THREAD) {
+                    float* q = gfrc + 3 * ct_geom(leg, slot);
+                    q[0] += r.v[CT_FORCE]; q[1] += r.v[CT_FORCE + 1]; q[2] += r.v[CT_FORCE + 2];
+                }
+                count += r.on ? 1u : 0u;
+            }
+        }
+        count = quad_sum_u(count);
+        const bool real = lblock * FW_EPW + quad < a.n && leg == 0;
+        if (f.ncon && real) f.ncon[(size_t)k * a.n + env] = (int)count;
+        if (f.unconv && real) f.unconv[(size_t)k * a.n + env] = s.fail > 0.f ? 1 : 0;
+    }
+    __syncthreads();
+    const int left = a.n - lblock * FW_EPW, n_es = left < FW_EPW ? left : FW_EPW;
+    const size_t es0 = (size_t)k * a.n + (size_t)lblock * FW_EPW;
+    auto store = [&](float* arr, int at, int len) {
+        if (!arr) return;
+        float* dst = arr + es0 * len;
+        ro_store_segment(dst, img + at, n_es * len, (((uintptr_t)dst) & 15u) == 0 ? 1 : 0, tid);
+    };
+    store(f.contact, CT_LDS_TABLE, CT_TABLE); store(f.geom_frc, CT_LDS_GEOM, CT_GEOMF);
+}
+
 // Self-check of the kernarg-segment reads above, run once per process before the first handle is handed out: a kernel with the step kernels'
 // argument list compares what it reads through kernarg_base() with the arguments it received by value.
 __global__ void jb_kernarg_probe_kernel(KArgs a, StepIO io, int* ok) {
@@ -853,6 +962,7 @@ struct jb_handle {
     Dev<float> d_tape, d_rows_stage, d_rew_stage;      // staging of the host-buffer rollouts (jb_step_many, jb_rollout_policy): grow-only
     Dev<unsigned char> d_done_stage;                   // jb_score_tapes_device: the done flags of every step, next to d_rew_stage (grow-only)
     Dev<float> d_readout_stage;                        // jb_readout: the outputs on their way to the host (grow-only)
+    Dev<float> d_contacts_stage;                       // jb_contacts: likewise
     Dev<float> d_forward_stage;                        // jb_forward: the actions on their way in, the outputs on their way out (grow-only)
     Dev<uint32_t> d_snap_stage; Dev<int> d_src_stage;  // jb_snapshot / jb_restore: the raw blocks and the index map on their way to / from the host (grow-only)
     Dev<int> d_wave_order;           // launch order of the waves (jb_wave_order_kernel), empty while the device holds the whole batch at once
@@ -997,6 +1107,16 @@ template <bool PAIR> static ForwardKernel forward_kernel() {
 #endif
     if constexpr (!built) return nullptr;
     else return jb_forward_kernel<PAIR>;
+}
+typedef void (*ContactsKernel)(KArgs, CtArgs);
+template <bool PAIR> static ContactsKernel contacts_kernel() {
+#ifdef JB_DEV_ONLY4
+    constexpr bool built = !PAIR;
+#else
+    constexpr bool built = true;
+#endif
+    if constexpr (!built) return nullptr;
+    else return jb_contacts_kernel<PAIR>;
 }
 static int kernel_variant(const KArgs& k) { return step_variant(k.lean, k.pair, k.per_env_model, k.epw); }
 static int check_variant(int lean, int pair, int per_env_model, int epw) {
@@ -1396,7 +1516,7 @@ int jb_release_staging(jb_handle* h) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
     h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset(); h->d_done_stage.reset();
-    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset(); h->d_forward_stage.reset();
+    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset(); h->d_forward_stage.reset(); h->d_contacts_stage.reset();
     return JB_OK;
 }
 // ---------------------------------------------------------------------------------------------- snapshot / restore / fork, tape scoring
@@ -1592,6 +1712,62 @@ int jb_forward(jb_handle* h, const float* ctrl, float* qacc, float* qfrc, float*
     if (qfrc) JB_HIP(hipMemcpyAsync(qfrc, d_qf, sizeof(float) * N * FW_NV, hipMemcpyDeviceToHost, h->stream));
     if (body_acc) JB_HIP(hipMemcpyAsync(body_acc, d_ba, sizeof(float) * N * FW_BACC, hipMemcpyDeviceToHost, h->stream));
     if (motor) JB_HIP(hipMemcpyAsync(motor, d_mo, sizeof(float) * N * FW_MOTOR, hipMemcpyDeviceToHost, h->stream));
+    if (unconverged) JB_HIP(hipMemcpyAsync(unconverged, d_un, N, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipStreamSynchronize(h->stream));
+    return JB_OK;
+}
+// The contact pass (jb_contacts_kernel above): the forward pass's launch with the output images behind the scratch and the tables in LDS.
+static_assert(JB_NCONTACT == CT_NROW && JB_CONTACT_WIDTH == CT_W, "the header states the table's shape");
+static_assert(step_lds_bytes(step_layout(FW_EPW, false, true), true) + 16 + CT_LDS_FLOATS * sizeof(float) <= 64 * 1024 &&
+              step_lds_bytes(step_layout(FW_EPW, false, false), true) + 16 + CT_LDS_FLOATS * sizeof(float) <= 64 * 1024, "scratch, tables and images fit a workgroup's 64 KB of LDS");
+int32_t jb_contact_rows(void) { return CT_NROW; }
+void jb_contact_slot_geoms(int32_t* out) { if (out) ct_slot_geoms(out); }
+int jb_contacts_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, const float* d_ctrl, float* d_contact, int32_t* d_ncon, float* d_geom_frc, uint8_t* d_unconverged) {
+    JB_ENTER(h);
+    if (n_snaps < 1) return fail(JB_E_INVALID, "jb_contacts_device: n_snaps must be >= 1");
+    if (!d_contact && !d_ncon && !d_geom_frc && !d_unconverged) return fail(JB_E_INVALID, "jb_contacts_device: all four outputs are NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_contacts_device: a jb_step_async is pending (jb_step_wait first)");
+    if (!d_snaps && n_snaps != 1) return fail(JB_E_INVALID, "jb_contacts_device: the handle's current state is ONE state (n_snaps must be 1 without a snapshot stack)");
+    const ContactsKernel kernel = h->ka.pair ? contacts_kernel<true>() : contacts_kernel<false>();
+    if (!kernel) return fail(JB_E_INVALID, "JB_DEV_ONLY4 build: only the contact pass without the pair contacts");
+    RoctxRange range("jb_contacts");
+    const int N = h->cfg.n_envs;
+    const StepLayout lay = step_layout(FW_EPW, false, h->ka.pair != 0);
+    KArgs a = h->ka;
+    a.epw = FW_EPW; a.lean = 0;      // the pass has its own layout, whichever kernel the handle steps with
+    CtArgs f;
+    f.first = d_snaps ? snap_view(const_cast<void*>(d_snaps), N) : state_view(h);      // (const_cast: the pass only reads)
+    f.stride_words = (long long)SNAP_WORDS * N;
+    f.waves_per_snap = (N + FW_EPW - 1) / FW_EPW;
+    const size_t step_bytes = step_lds_bytes(lay, h->ka.per_env_model != 0);
+    f.img = (int)((step_bytes + 15) / 16 * 4);
+    f.ctrl = d_ctrl;
+    f.contact = d_contact; f.geom_frc = d_geom_frc; f.ncon = d_ncon; f.unconv = d_unconverged;
+    const long long blocks = (long long)n_snaps * f.waves_per_snap;
+    if (blocks > 0x7fffffffLL) return fail(JB_E_INVALID, "jb_contacts_device: too many env-states for one launch");
+    const size_t lds_bytes = ((size_t)f.img + CT_LDS_FLOATS) * sizeof(float);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), lds_bytes, h->stream, a, f);
+    JB_HIP(hipGetLastError());
+    return JB_OK;
+}
+int jb_contacts(jb_handle* h, const float* ctrl, float* contact, int32_t* ncon, float* geom_frc, uint8_t* unconverged) {
+    JB_ENTER(h);
+    if (!contact && !ncon && !geom_frc && !unconverged) return fail(JB_E_INVALID, "jb_contacts: all four outputs are NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, "jb_contacts: a jb_step_async is pending (jb_step_wait first)");
+    const size_t N = (size_t)h->cfg.n_envs;
+    int rc = grow_stage(h, h->d_contacts_stage, N * (size_t)(CT_TABLE + CT_GEOMF + 2) + (N + 3) / 4, "the contact pass");
+    if (rc) return rc;
+    float* d_ct = h->d_contacts_stage.get();
+    float* d_gf = d_ct + N * CT_TABLE;
+    float* d_u = d_gf + N * CT_GEOMF;
+    int32_t* d_nc = (int32_t*)(d_u + N);
+    uint8_t* d_un = (uint8_t*)(d_nc + N);
+    if (ctrl) JB_HIP(hipMemcpyAsync(d_u, ctrl, sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
+    rc = jb_contacts_device(h, nullptr, 1, ctrl ? d_u : nullptr, contact ? d_ct : nullptr, ncon ? d_nc : nullptr, geom_frc ? d_gf : nullptr, unconverged ? d_un : nullptr);
+    if (rc) return rc;
+    if (contact) JB_HIP(hipMemcpyAsync(contact, d_ct, sizeof(float) * N * CT_TABLE, hipMemcpyDeviceToHost, h->stream));
+    if (ncon) JB_HIP(hipMemcpyAsync(ncon, d_nc, sizeof(int32_t) * N, hipMemcpyDeviceToHost, h->stream));
+    if (geom_frc) JB_HIP(hipMemcpyAsync(geom_frc, d_gf, sizeof(float) * N * CT_GEOMF, hipMemcpyDeviceToHost, h->stream));
     if (unconverged) JB_HIP(hipMemcpyAsync(unconverged, d_un, N, hipMemcpyDeviceToHost, h->stream));
     JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;

@@ -2337,8 +2337,27 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
 }
 
 // ----------------------------------------------------------------------------- the substep
-template <typename V, bool PAIR = false>
-JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>& s, const V& ctrl, const SimOpts& o, const bool xtra, const bool xbody, const Mat3<V>& Rw) {
+// A caller that wants to read the scratch after a substep (jb_contacts.hpp) must know what the substep alone knows: which slots were live
+// (the entries are packed by rank), and - where the wave solved its contact problem a second time - the first solve's minimiser (SC_Y, which
+// the second solve overwrites for every env of the wave) and which envs took the second solve's.  It passes a tap; the step kernels pass none,
+// and NoTap's empty calls leave their code as it is.
+struct NoTap {
+    JB_HD void live(unsigned) const {}
+    template <typename V> JB_HD void first_solve(const LaneScratch<V>&) const {}
+    template <typename MKT> JB_HD void resolved(const MKT&) const {}
+};
+template <typename V> struct SolveTap {
+    unsigned* live_slots; bool* redone; V* y1 /*[9]: SC_Y after the first solve*/; typename lane_traits<V>::mask* re /*this env took the second solve*/;
+    JB_HD void live(unsigned l) const { *live_slots = l; }
+    JB_HD void first_solve(const LaneScratch<V>& sc) const {
+        *redone = true;
+#pragma unroll
+        for (int i = 0; i < 9; i++) y1[i] = sc.ld(SC_Y + i);
+    }
+    JB_HD void resolved(const typename lane_traits<V>::mask& r) const { *re = r; }
+};
+template <typename V, bool PAIR = false, typename Tap = NoTap>
+JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>& s, const V& ctrl, const SimOpts& o, const bool xtra, const bool xbody, const Mat3<V>& Rw, const Tap& tap = Tap()) {
     using MK = typename lane_traits<V>::mask;
     using U = typename lane_traits<V>::uint;
     const V h = m.c[LM_H];
@@ -2749,6 +2768,7 @@ JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
     // the helper groups learn what phase A found (values of the first lane, a main lane)
     any_contact = wave_bcast_u(any_contact ? 1u : 0u) != 0u;
     live_slots = wave_bcast_u(live_slots);
+    tap.live(live_slots);
     wave_sync();          // phase A's scratch (SC_OWN, SC_ST, SC_DD, the candidate rows: written under `if (rep)`) -> read by every group below
     const SlotPlan plan = make_slot_plan(sc, live_slots);
     const SpreadPlan<V> spl = make_spread_plan<V>(sc, plan, o.spread != 0 && any_contact);
@@ -2786,6 +2806,7 @@ JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
     // few in ten million - pay one scalar branch.
     if (__builtin_expect(redone, false)) {
         JB_ASM_MARK("jb-cold-solve-begin");          // (a comment in the ISA: tools/asm_spills.py tells the cold block's register spills from the hot loop's)
+        tap.first_solve(sc);
         const U cf = group_sum_u<V>(sc, mbit(capped));      // every lane group learns which envs it concerns (helper lanes contribute zeros)
         Pk2<V> zr[3];
         V zl[2], zm;
@@ -2793,6 +2814,7 @@ JB_HD bool substep_impl(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
         (void)newton_phase<V, PAIR, true>(m, sc, s, o, xtra, plan, spl, Rw, sys, dk, any_contact, env_con, zr, zl, zm, capped2);
         const U cf2 = group_sum_u<V>(sc, mbit(capped2));
         const MK re = neq_u(cf, zero_u<V>());
+        tap.resolved(re);
 #pragma unroll
         for (int ip = 0; ip < 3; ip++) yrp[ip] = selw(re, zr[ip], yrp[ip]);
         yl[0] = sel(re, zl[0], yl[0]); yl[1] = sel(re, zl[1], yl[1]); ym = sel(re, zm, ym);
@@ -2884,8 +2906,8 @@ template <typename V> JB_HD void normalise_state(LaneState<V>& s) {
 // One physics substep.  A wave-uniform broadphase decides whether only the foot sphere + lower-leg cylinder can
 // touch the floor (common) or every geom of the model has to be tested (rare).  Returns (wave-uniform) whether the contact solve ran a
 // second time with the exact line search (newton_phase).
-template <typename V, bool PAIR = false>
-JB_HD bool substep(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>& s, const V& ctrl, const SimOpts& o) {
+template <typename V, bool PAIR = false, typename Tap = NoTap>
+JB_HD bool substep(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>& s, const V& ctrl, const SimOpts& o, const Tap& tap = Tap()) {
     unsigned xt = 0;          // bit 0: some upper leg may touch the floor, bit 1: some root / motor-body geom may
     Mat3<V> Rw;               // root rotation (main lanes): mj_kinematics normalises the quaternion first
 #if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
@@ -2922,7 +2944,7 @@ JB_HD bool substep(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>
 #ifdef JB_WAVE_STATS
     if (xtra && sc.grp == 0) s.st_xtra = s.st_xtra + V(1);
 #endif
-    return substep_impl<V, PAIR>(m, sc, s, ctrl, o, xtra, xbody, Rw);
+    return substep_impl<V, PAIR, Tap>(m, sc, s, ctrl, o, xtra, xbody, Rw, tap);
 }
 
 }  // namespace jb

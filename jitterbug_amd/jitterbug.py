@@ -91,6 +91,34 @@ class _NamedData:
         self.sensordata = _Indexer(lambda k: {"jitterbug_framelinvel": ph.jitterbug_framelinvel()}[k])
 
 
+class _Contact:
+    """one record of physics.data.contact, MuJoCo's field names: dist, pos [3], frame [9] (the normal first), geom1, geom2 (-1: the floor)"""
+
+    def __init__(self, dist, pos, normal, geom1, geom2):
+        n = np.asarray(normal, dtype=np.float64)
+        y = np.array([0.0, 1.0, 0.0]) if abs(n[1]) < 0.5 else np.array([0.0, 0.0, 1.0])          # mju_makeFrame
+        y = y - n * (n @ y)
+        y /= np.linalg.norm(y)
+        self.dist, self.pos, self.geom1, self.geom2 = float(dist), np.asarray(pos, dtype=np.float64).copy(), int(geom1), int(geom2)
+        self.frame = np.concatenate([n, y, np.cross(n, y)])
+
+
+class _Data:
+    """physics.data: ncon and contact of the current state under a zero action (JitterbugVecEnv.contacts)"""
+
+    def __init__(self, ph):
+        self._ph = ph
+
+    @property
+    def ncon(self):
+        return len(self._ph._contacts()["dist"])
+
+    @property
+    def contact(self):
+        c = self._ph._contacts()
+        return [_Contact(c["dist"][i], c["pos"][i], c["normal"][i], c["geom1"][i], c["geom2"][i]) for i in range(len(c["dist"]))]
+
+
 class _Named:
     def __init__(self, ph):
         self.data = _NamedData(ph)
@@ -107,7 +135,10 @@ class Physics:
         self._i = index
         self._cache = None
         self._cache_version = -1
+        self._contacts_cache = None
+        self._contacts_version = -1
         self.named = _Named(self)
+        self.data = _Data(self)
 
     def _state(self):
         if self._cache is None or self._cache_version != self._venv.state_version:
@@ -131,6 +162,28 @@ class Physics:
         a[self._i] = float(np.asarray(action, dtype=np.float64).reshape(-1)[0])
         out = self._venv.forward(a, qacc=True, qfrc=True)
         return {"qacc": out["qacc"][self._i].copy(), "qfrc_constraint": out["qfrc_constraint"][self._i].copy()}
+
+    def contacts(self, action=0.0):
+        """This env's contacts under `action`, without advancing time: the active rows of JitterbugVecEnv.contacts as a dict - 'geom1',
+        'geom2' (model.GEOM_NAMES indices, geom1 -1: the floor), 'slot', 'pos', 'normal', 'force' [ncon, 3] in world axes (the force on
+        geom2), 'dist', 'fn' [ncon] (the other envs of the batch are evaluated with action 0)."""
+        a = np.zeros(self._venv.num_envs, dtype=np.float32)
+        a[self._i] = float(np.asarray(action, dtype=np.float64).reshape(-1)[0])
+        return self._venv.contacts(a, envs=(self._i,))["list"][0]      # (the pass is the batch's; only this env's rows are listed)
+
+    def _contacts(self):
+        """the current state's contacts under a zero action, cached like the state"""
+        if self._contacts_cache is None or self._contacts_version != self._venv.state_version:
+            self._contacts_cache = self.contacts(0.0)
+            self._contacts_version = self._venv.state_version
+        return self._contacts_cache
+
+    def contact_force(self, i):
+        """[fn, ft1, ft2] of contact i of physics.data.contact: the force along its frame's normal and two tangents, as the first three
+        entries of dm_control's physics.data.contact_force(i)."""
+        c = self._contacts()
+        f = _Contact(c["dist"][i], c["pos"][i], c["normal"][i], c["geom1"][i], c["geom2"][i]).frame.reshape(3, 3)
+        return f @ np.asarray(c["force"][i], dtype=np.float64)
 
     @property
     def _params(self):

@@ -47,6 +47,8 @@ GEOM_NAMES = (("coreBody1", "coreBody2", "screw1", "screw2")
               + tuple(n for leg in model_spec.LEG_NAMES for n in (leg + "upper_cyl", leg + "_tip", leg + "lower_cyl", "foot" + leg[3:]))
               + ("threadMass", "mass"))
 FOOT_GEOMS = tuple(7 + 4 * l for l in range(NLEG))      # the foot spheres, in model_spec.LEG_NAMES order
+# a contact pass's dense table (jb_contacts): rows (the candidate slots of the step kernels' collision phase), floats per row
+NCONTACT, CONTACT_WIDTH = 74, 12
 # rows of a readout's `frames` (jb_readout): the ten bodies, the 22 geoms, the target
 NFRAME = NBODY + NGEOM + 1
 FRAME_GEOM0, FRAME_TARGET = NBODY, NBODY + NGEOM

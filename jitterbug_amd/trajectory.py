@@ -15,10 +15,13 @@ class Trajectory:
     """frames [K+1, N, 33, 12] and clearance [K+1, N, 22] (float32 torch device tensors; rows as JitterbugVecEnv.readout gives them),
     snapshots [K+1, snapshot_bytes] (uint8: the stack itself - restore_device row k to continue from step k) and the packed rows
     [K, N, D+2] = [obs | reward | done] of the steps.  qfrc [K, N, 15] (record(..., forces=True), else None): the contact forces in joint
-    space at the state BEFORE step k under action k, as JitterbugVecEnv.forward gives them (0-2: the ground reaction in world axes)."""
+    space at the state BEFORE step k under action k, as JitterbugVecEnv.forward gives them (0-2: the ground reaction in world axes).
+    geom_frc [K, N, 22, 3] and ncon [K, N] (record(..., contacts=True), else None): the floor's force on each geom and the number of
+    contacts at the state BEFORE step k under action k, as JitterbugVecEnv.contacts gives them."""
 
-    def __init__(self, frames, clearance, snapshots, rows, params, qfrc=None):
+    def __init__(self, frames, clearance, snapshots, rows, params, qfrc=None, geom_frc=None, ncon=None):
         self.frames, self.clearance, self.snapshots, self.rows, self.qfrc = frames, clearance, snapshots, rows, qfrc
+        self.geom_frc, self.ncon = geom_frc, ncon
         self._params = params          # env index -> float64[NPARAM] table that env was simulated with
 
     @property
@@ -28,29 +31,32 @@ class Trajectory:
     def save_npz(self, path, envs):
         """Write envs `envs` (a list of indices): frames [K+1, E, 33, 12], clearance [K+1, E, 22], geom_type [E, 22]
         (0 sphere, 1 cylinder, 2 box, 3 ellipsoid) and geom_size [E, 22, 3] from the envs' model tables, frame_names [33], geom_names [22],
-        body_names [10], envs [E]; with recorded forces also qfrc [K, E, 15]."""
+        body_names [10], envs [E]; with recorded forces also qfrc [K, E, 15], with recorded contacts geom_frc [K, E, 22, 3] and ncon [K, E]."""
         envs = [int(e) for e in envs]
         P = np.stack([np.asarray(self._params(e), dtype=np.float64) for e in envs])
         g = P[:, model.P_GEOM:model.P_GEOM + model.NGEOM * model.GEOM_STRIDE].reshape(len(envs), model.NGEOM, model.GEOM_STRIDE)
         idx = self.frames.new_tensor(envs).long()
         extra = {} if self.qfrc is None else dict(qfrc=self.qfrc.index_select(1, idx).cpu().numpy())
+        if self.geom_frc is not None:
+            extra.update(geom_frc=self.geom_frc.index_select(1, idx).cpu().numpy(), ncon=self.ncon.index_select(1, idx).cpu().numpy())
         np.savez(path, frames=self.frames.index_select(1, idx).cpu().numpy(), clearance=self.clearance.index_select(1, idx).cpu().numpy(),
                  geom_type=g[:, :, model.G_TYPE].astype(np.int32), geom_size=g[:, :, model.G_SIZE:model.G_SIZE + 3].copy(),
                  frame_names=np.array(model.BODY_NAMES + model.GEOM_NAMES + ("target",)), geom_names=np.array(model.GEOM_NAMES),
                  body_names=np.array(model.BODY_NAMES), envs=np.array(envs, dtype=np.int64), **extra)
 
 
-def record(venv, n_steps, actions=None, forces=False):
+def record(venv, n_steps, actions=None, forces=False, contacts=False):
     """Step `venv` n_steps times - with the action tape `actions` [n_steps, N], or with the task's heuristic policy evaluated in the step
     kernel when None - and return the Trajectory.  The steps are the ordinary single-step launches: the env ends in the state, and with
     the rows, n_steps calls of step would have produced; snapshots and the readout only read.  forces=True (needs the action tape): ONE
     forward pass (JitterbugVecEnv.forward_device) over snapshots 0 .. K-1 with the tape keeps qfrc [K, N, 15] - row k is what a live forward
-    before step k with action k would have given, bit for bit."""
+    before step k with action k would have given, bit for bit.  contacts=True (needs the tape too): ONE contact pass
+    (JitterbugVecEnv.contacts_device) over the same snapshots keeps geom_frc [K, N, 22, 3] and ncon [K, N], row k likewise."""
     import torch
     K, N = int(n_steps), venv.num_envs
     assert K >= 0
-    if forces and actions is None:
-        raise ValueError("record(forces=True) needs the action tape: the heuristic policy's actions stay inside the step kernel")
+    if (forces or contacts) and actions is None:
+        raise ValueError("record(forces=True / contacts=True) needs the action tape: the heuristic policy's actions stay inside the step kernel")
     dev = torch.device("cuda", int(venv.cfg.device_id))
     cur = torch.cuda.current_stream(dev)
     env_stream = torch.cuda.ExternalStream(int(venv.stream), device=dev) if venv.stream else torch.cuda.default_stream(dev)
@@ -73,6 +79,12 @@ def record(venv, n_steps, actions=None, forces=False):
         qfrc = torch.empty((K, N, model.NV), dtype=torch.float32, device=dev)
         if K > 0:
             venv.forward_device(tape.data_ptr(), qfrc_ptr=qfrc.data_ptr(), snaps_ptr=snaps.data_ptr(), n_snaps=K)
+    geom_frc = ncon = None
+    if contacts:
+        geom_frc = torch.empty((K, N, model.NGEOM, 3), dtype=torch.float32, device=dev)
+        ncon = torch.empty((K, N), dtype=torch.int32, device=dev)
+        if K > 0:
+            venv.contacts_device(tape.data_ptr(), ncon_ptr=ncon.data_ptr(), geom_frc_ptr=geom_frc.data_ptr(), snaps_ptr=snaps.data_ptr(), n_snaps=K)
     cur.wait_stream(env_stream)
     venv.synchronize()
-    return Trajectory(frames, clearance, snaps, rows, venv.model_params, qfrc)
+    return Trajectory(frames, clearance, snaps, rows, venv.model_params, qfrc, geom_frc, ncon)

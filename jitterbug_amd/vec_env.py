@@ -521,6 +521,57 @@ class JitterbugVecEnv:
         """float32 [N, 3]: the net force of the floor on each robot in world axes, newtons (rows 0-2 of forward()'s 'qfrc_constraint')."""
         return self.forward(actions, qacc=False, qfrc=True)["qfrc_constraint"][:, 0:3].copy()
 
+    # ---- contacts: which contacts the current state has and the force in each, without advancing time (jb_contacts / jb_contacts_device)
+    @staticmethod
+    def contact_slot_geoms():
+        """int32 [model.NCONTACT, 2]: (geom1, geom2) of every row of the dense contact table, geoms in model.GEOM_NAMES order, geom1 = -1
+        for the floor; a pair row is (the leg's upper cylinder, threadMass or mass).  Fixed by the library."""
+        L = _lib.load()
+        if L.jb_contact_rows() != model.NCONTACT:
+            raise _lib.JitterbugHipError("the library's contact table has %d rows, model.NCONTACT says %d" % (L.jb_contact_rows(), model.NCONTACT))
+        out = np.zeros((model.NCONTACT, 2), dtype=np.int32)
+        L.jb_contact_slot_geoms(_lib.ptr(out))
+        return out
+
+    def contacts(self, actions=None, envs=None):
+        """The contacts of the current state under `actions` (None: 0) - MuJoCo's data.contact with mj_contactForce - as a dict:
+        'ncon' int32 [N]; 'contact' float32 [N, model.NCONTACT, 12], the dense table = [pos(3) | normal(3) | force(3) | dist | fn | active]
+        per candidate slot in world axes (normal from geom1 to geom2, +z for the floor; force on geom2; an inactive row is zeros);
+        'geom_frc' float32 [N, 22, 3] the world force of the floor on each geom; 'unconverged' bool [N]; 'slot_geoms' int32
+        [model.NCONTACT, 2]; and 'list': per env of `envs` (None: every env, in order) a dict of the active rows only - 'geom1', 'geom2'
+        int32 [ncon], 'slot' (the row's index), 'pos', 'normal', 'force' [ncon, 3], 'dist', 'fn' [ncon].  The contacts are those the first
+        substep of a step would solve, from the solve behind forward()'s 'qacc'.  The state, the counters and the solver statistics are
+        left as they are."""
+        n = self.num_envs
+        a = None if actions is None else np.ascontiguousarray(np.broadcast_to(np.asarray(actions, dtype=np.float32).reshape(-1), (n,)))
+        table = np.empty((n, model.NCONTACT, model.CONTACT_WIDTH), dtype=np.float32)
+        ncon, gf, unc = np.empty(n, dtype=np.int32), np.empty((n, model.NGEOM, 3), dtype=np.float32), np.empty(n, dtype=np.uint8)
+        _lib.check(self._L.jb_contacts(self._h, _lib.ptr(a), _lib.ptr(table), _lib.ptr(ncon), _lib.ptr(gf), _lib.ptr(unc)))
+        geoms = self.contact_slot_geoms()
+        rows = []
+        for j in (range(n) if envs is None else [int(e) for e in envs]):
+            act = np.nonzero(table[j, :, 11] != 0)[0]
+            t = table[j, act]
+            rows.append(dict(slot=act.astype(np.int32), geom1=geoms[act, 0], geom2=geoms[act, 1], pos=t[:, 0:3], normal=t[:, 3:6], force=t[:, 6:9], dist=t[:, 9], fn=t[:, 10]))
+        return dict(ncon=ncon, contact=table, geom_frc=gf, unconverged=unc.view(np.bool_), slot_geoms=geoms, list=rows)
+
+    def contacts_device(self, ctrl_ptr=None, contact_ptr=None, ncon_ptr=None, geom_frc_ptr=None, unconverged_ptr=None, snaps_ptr=None, n_snaps=1):
+        """The same pass on device pointers (contact float32 [n_snaps * N, model.NCONTACT, 12], ncon int32, geom_frc float32
+        [n_snaps * N, 22, 3], unconverged uint8; None = absent: no stores; ctrl None = 0), asynchronous.  snaps_ptr: a stack of `n_snaps`
+        device snapshots back to back (`snapshot_bytes` apart) instead of the current state; env-state k * N + j is env j of snapshot k.
+        An env-state's result never depends on its snapshot's place in the stack or on the outputs present.  It depends on the other envs
+        of its wave only where the substep underneath does (spread sweeps: some states with many contacts, 3e-7 relative; forward_device
+        runs the same substep); on an env created with flags=_lib.FLAG_NO_SPREAD it does not, bit for bit."""
+        _lib.check(self._L.jb_contacts_device(self._h, snaps_ptr, int(n_snaps), ctrl_ptr, contact_ptr, ncon_ptr, geom_frc_ptr, unconverged_ptr))
+
+    def foot_forces(self, actions=None):
+        """float32 [N, 4, 3]: the world force of the floor on each foot sphere, newtons, in model_spec.LEG_NAMES order."""
+        n = self.num_envs
+        a = None if actions is None else np.ascontiguousarray(np.broadcast_to(np.asarray(actions, dtype=np.float32).reshape(-1), (n,)))
+        gf = np.empty((n, model.NGEOM, 3), dtype=np.float32)
+        _lib.check(self._L.jb_contacts(self._h, _lib.ptr(a), None, None, _lib.ptr(gf), None))
+        return gf[:, model.FOOT_GEOMS].copy()
+
     # ---- rows between GPUs through the library's own RCCL binding (jb_comm_*: no torch.distributed on the data path)
     @staticmethod
     def comm_unique_id():
