@@ -297,7 +297,7 @@ __device__ __forceinline__ void step_body(KArgs a, StepIO io) {
     s.st_xtra = 0.f; s.st_sweeps = 0.f; s.st_contact = 0.f; s.st_slots = 0.f; s.st_fast = 0.f; s.st_checks = 0.f;
 #endif
     SimOpts o; o.contacts = a.contacts; o.max_newton = a.max_newton; o.implicit_damp = 1; o.rank_one = a.rank_one; o.lean = LEAN ? 1 : 0; o.offload = OFFLOAD ? 1 : 0; o.spread = a.spread; o.prof = nullptr; o.hist = nullptr;
-    o.aux = aux_on ? 1 : 0; o.fuse_rows = LAY.fused_row_build ? 1 : 0; o.every_lane_update = LAY.every_lane_update ? 1 : 0;
+    o.aux = aux_on ? 1 : 0; o.fuse_rows = LAY.fused_row_build ? 1 : 0; o.every_lane_update = LAY.every_lane_update ? 1 : 0; o.scalar_votes = LAY.scalar_votes ? 1 : 0;
 #ifdef JB_CAPTURE
     o.capture = a.capture; o.capture_count = a.capture_count;
 #endif
@@ -409,11 +409,16 @@ __device__ __forceinline__ void step_body(KArgs a, StepIO io) {
     {
         KArgs af;                 // the fields store_state reads
         af.n = ka->n; af.root = ka->root; af.leg = ka->leg;
-        store_state(af, env, lane, leg, s);
+        // StepLayout::late_env_index: the env index as a value of its own, so that the addresses below are formed HERE.  Left to itself the
+        // compiler keeps the 64-bit byte offset of the loads at the kernel's entry alive through every loop for these stores - a register
+        // pair that the substep loop with its scalar votes has no room for (one spill at the entry, one reload here).
+        int env_out = env;
+        if (LAY.late_env_index) asm volatile("" : "+v"(env_out));
+        store_state(af, env_out, env_out * 4 + leg, leg, s);
         if (leg == 0) {
-            ka->step_count[env] = er.step_count;
-            ka->episode[env] = er.episode;
-            af.root[(RF_TGT + 0) * af.n + env] = er.tgt[0]; af.root[(RF_TGT + 1) * af.n + env] = er.tgt[1]; af.root[(RF_TGT + 2) * af.n + env] = er.tgt[2];
+            ka->step_count[env_out] = er.step_count;
+            ka->episode[env_out] = er.episode;
+            af.root[(RF_TGT + 0) * af.n + env_out] = er.tgt[0]; af.root[(RF_TGT + 1) * af.n + env_out] = er.tgt[1]; af.root[(RF_TGT + 2) * af.n + env_out] = er.tgt[2];
         }
     }
     unsigned long long* const wc = ic->wave_clock;

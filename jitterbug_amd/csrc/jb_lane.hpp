@@ -119,6 +119,12 @@ template <int J> JB_D float quad_bcast(float x) { return __builtin_bit_cast(floa
 JB_D float xor_sum(float x, int off, bool sym2) { return __builtin_bit_cast(float, xor_sum_bits(__builtin_bit_cast(unsigned, x), off, sym2, true)); }
 JB_D unsigned xor_sum_u(unsigned x, int off, bool sym2) { return xor_sum_bits(x, off, sym2, false); }
 JB_D unsigned wave_bcast_u(unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); }   // value of the first active lane
+// A vote of the MAIN lanes (lane group 0, lanes 0 .. gstride-1) that every lane of the wave takes part in: the ballot of `m` restricted to
+// group 0.  The result is wave-uniform and is born in scalar registers - the caller needs no `if (is_main)` around the vote and no
+// wave_bcast_u to hand the answer to the helper groups (a wave-uniform value assigned under a divergent predicate becomes a vector value,
+// and fetching it back costs a v_readfirstlane round trip).  What a helper lane holds in `m` never counts.  (The restriction is a scalar
+// AND of the ballot with a constant: `grp == 0 && m` inside the ballot sends the combined mask through a v_cndmask / v_cmp pair.)
+template <typename SC> JB_D bool main_vote(const SC& sc, bool m) { return (__builtin_amdgcn_ballot_w64(m) & ((1ull << sc.gstride) - 1ull)) != 0ull; }
 // Hand-over point between lane groups through the scratch (one group wrote, another reads).  The groups are lanes of ONE wave and
 // LDS operations of a wave complete in program order, so the hardware needs nothing here - but the COMPILER must not move a read of
 // the hand-over across the writes it depends on (it sees one thread and may prove the addresses different once the group is known):
@@ -365,6 +371,8 @@ inline unsigned wave_bcast_u(unsigned x) {           // the first lane of the wa
     return r;
 }
 inline bool any_lane(bool m) { return m; }
+// the main lanes' vote (see the device's): group 0's any_lane, handed to the other group threads through the mailbox
+template <typename SC, typename MK> inline bool main_vote(const SC&, const MK& m) { return wave_bcast_u(any_lane(m) ? 1u : 0u) != 0u; }
 inline float quad_sum(float x) { return x; }
 inline double quad_sum(double x) { return x; }
 template <typename T> inline Quad<T> sel(const Mask4& m, const Quad<T>& a, const Quad<T>& b) { Quad<T> r; for (int i = 0; i < 4; i++) r.v[i] = m.v[i] ? a.v[i] : b.v[i]; return r; }

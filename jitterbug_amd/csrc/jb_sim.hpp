@@ -1771,6 +1771,9 @@ struct SimOpts {
                          //    their own before it (StepLayout::fused_row_build: the variants that would spill).  Same arithmetic, same bits.
     int every_lane_update = 1;   // 1: the iterate's update after star_solve (newton_phase) is made by every lane, only its stores by the main lanes; 0: under
                          //    the main lanes' predicate (StepLayout::every_lane_update: the variants that would spill).  Same arithmetic, same bits.
+    int scalar_votes = 1;        // 1: the wave-uniform decisions after a check of the active set (newton_phase) and of the broadphase (substep)
+                         //    are votes of the main lanes that every lane takes (main_vote): they never leave the scalar registers; 0: taken under the
+                         //    main lanes' predicate and fetched back with wave_bcast_u (StepLayout::scalar_votes, -DJB_VECTOR_VOTES).  Same bits.
     float* capture = nullptr;           // diagnostic builds (-DJB_CAPTURE): ring of JB_CAPTURE_SLOTS records x 64 floats - the entry state of substeps whose contact solve stayed
     unsigned* capture_count = nullptr;  //   unconverged after the line-searched pass (substep_impl), and how many there were
     unsigned long long* prof;   // diagnostic builds: per-wave cycle accumulators [phaseA, check sweeps, full sweeps, solves, integrate]
@@ -2198,7 +2201,6 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
 #ifdef JB_WAVE_STATS
                     if (is_main) s.st_checks = s.st_checks + V(1);
 #endif
-                    unsigned fin = 0u, full = 1u;
                     if (JB_GROUP_MERGE(is_main)) {      // (the records' comparison is register-only: every lane; the votes below keep to the main lanes)
                         MK changed = mor(mor(neq_u(acc.bw0, prev_bw0), neq_u(acc.bw1, prev_bw1)), neq_u(acc.xh, prev_xh));
                         unconverged = neq_u(quad_sum_u(mbit(changed)), zero_u<V>());
@@ -2211,8 +2213,8 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                             unconverged = mand(mor(unconverged, shortened), mnot(settled));
                         }
                     }
-                    if (is_main) {
 #if defined(JB_WAVE_STATS) && defined(__HIPCC__)
+                    if (is_main) {
                                             if (!LS && o.hist && !xtra) {      // how many active-set bits flipped per unconverged env (ordinary substeps: exact records)
                                                 const unsigned fl = quad_sum_u((unsigned)__builtin_popcount(acc.bw0 ^ prev_bw0));
                                                 const bool unc = unconverged;
@@ -2232,47 +2234,94 @@ JB_HD bool newton_phase(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneSta
                                                     if (m_multi && !m_bad) o.hist[52] += 1ull;          // a changed-set check that needs a full pass today and would not with per-lane rank-k
                                                 }
                                             }
+                    }
 #endif
-                        if (!any_lane(unconverged) || it >= cap) {
-                            capped = unconverged;                      // (all false unless the cap ended the iteration)
-                            fin = any_lane(unconverged) ? 2u : 1u;
+                    if (o.scalar_votes) {
+                        // Scalar votes (StepLayout::scalar_votes): the decisions below are the MAIN lanes' - main_vote counts no other lane - but
+                        // every lane takes them and the register-only work between them (the records' decode, the rank-one pass, its selects),
+                        // the helper groups on whatever they hold.  `final_pass`, `full_pass` and `wave_capped` are ballot results and stay in
+                        // scalar registers; nothing of a helper lane reaches a store, a vote or an address outside the row cache.
+                        const bool any_unc = main_vote(sc, unconverged);
+                        if (!any_unc || it >= cap) {
+                            if (is_main) capped = unconverged;         // (all false unless the cap ended the iteration)
+                            final_pass = true;
+                            wave_capped = any_unc;
+                            full_pass = true;
                         } else {
-                            // An env whose set differs from the factored one by a single pyramid edge of a leg slot (exact
-                            // records) takes a rank-one pass; the decision is the ENV's own (its records, its factorisation),
-                            // so its arithmetic never depends on its wave-mates.  A full pass runs only if some env needs one.
                             const U dfl = xor_u(acc.bw0, prev_bw0), dfl1 = xor_u(acc.bw1, prev_bw1);
                             const MK one_flip = eq_u(quad_sum_u(popc_u(dfl) + popc_u(dfl1)), zero_u<V>() + 1u);
                             const MK xh_same = eq_u(quad_sum_u(mbit(neq_u(acc.xh, prev_xh))), zero_u<V>());
                             U f_entry;
                             MK f_is, f_plus, f_tan2, f_on;
                             flip_decode(dfl, dfl1, acc.bw0, acc.bw1, plan.live, f_entry, f_is, f_plus, f_tan2, f_on);
-                            // the flipped contact's row must be in the row cache (beyond ROW_K live slots rows are rebuilt per pass)
                             const MK undecodable = mand(neq_u(or_u(dfl, dfl1), zero_u<V>()), mnot(mand(f_is, lt_u(f_entry, (unsigned)ROW_K))));
                             const MK rows_ok = eq_u(quad_sum_u(mbit(undecodable)), zero_u<V>());
                             fast_env = mand(mand(unconverged, fac_valid), mand(mand(one_flip, xh_same), rows_ok));
-                            if (LS || !o.rank_one) fast_env = lt(V(1), V(0));      // (the line-searched iteration works on full passes)
-                            full = any_lane(mand(unconverged, mnot(fast_env))) ? 1u : 0u;
-                            if (!LS && any_lane(fast_env)) {
+                            if (LS || !o.rank_one) fast_env = lt(V(1), V(0));
+                            full_pass = main_vote(sc, mand(unconverged, mnot(fast_env)));
+                            if (!LS && main_vote(sc, fast_env)) {
                                 W fyr[3];
                                 V fyl[2], fym;
                                 if (o.lean) { fac_load(sc, fac); if (PAIR) fac_load_cx(sc, fac); }
-                                rank_one_pass<V, PAIR>(sc, fac, dk, m.c[LM_MU], f_entry, f_is, f_plus, f_tan2, f_on, yr, yl, ym, fyr, fyl, fym);
+                                // a lane of a rank-one env reads a cached row (rows_ok); every other lane - a helper lane's records are junk - reads
+                                // a row that exists, entry 0, and its result is selected away
+                                const U r_entry = selu(lt_u(f_entry, (unsigned)ROW_K), f_entry, zero_u<V>());
+                                rank_one_pass<V, PAIR>(sc, fac, dk, m.c[LM_MU], r_entry, f_is, f_plus, f_tan2, f_on, yr, yl, ym, fyr, fyl, fym);
 #pragma unroll
                                 for (int ip = 0; ip < 3; ip++) yr[ip] = selw(fast_env, fyr[ip], yr[ip]);
                                 yl[0] = sel(fast_env, fyl[0], yl[0]); yl[1] = sel(fast_env, fyl[1], yl[1]); ym = sel(fast_env, fym, ym);
 #ifdef JB_WAVE_STATS
-                                s.st_fast = s.st_fast + V(1);
+                                if (is_main) s.st_fast = s.st_fast + V(1);
 #endif
                             }
                             prev_bw0 = acc.bw0; prev_bw1 = acc.bw1; prev_xh = acc.xh;      // the sets the new iterates are solved for
                         }
+                    } else {
+                        // The reference form (-DJB_VECTOR_VOTES, and the rows whose register budget objects): the decisions under the main lanes'
+                        // predicate, handed to the helper groups as values of the first lane.
+                        unsigned fin = 0u, full = 1u;
+                        if (is_main) {
+                            if (!any_lane(unconverged) || it >= cap) {
+                                capped = unconverged;                      // (all false unless the cap ended the iteration)
+                                fin = any_lane(unconverged) ? 2u : 1u;
+                            } else {
+                                // An env whose set differs from the factored one by a single pyramid edge of a leg slot (exact
+                                // records) takes a rank-one pass; the decision is the ENV's own (its records, its factorisation),
+                                // so its arithmetic never depends on its wave-mates.  A full pass runs only if some env needs one.
+                                const U dfl = xor_u(acc.bw0, prev_bw0), dfl1 = xor_u(acc.bw1, prev_bw1);
+                                const MK one_flip = eq_u(quad_sum_u(popc_u(dfl) + popc_u(dfl1)), zero_u<V>() + 1u);
+                                const MK xh_same = eq_u(quad_sum_u(mbit(neq_u(acc.xh, prev_xh))), zero_u<V>());
+                                U f_entry;
+                                MK f_is, f_plus, f_tan2, f_on;
+                                flip_decode(dfl, dfl1, acc.bw0, acc.bw1, plan.live, f_entry, f_is, f_plus, f_tan2, f_on);
+                                // the flipped contact's row must be in the row cache (beyond ROW_K live slots rows are rebuilt per pass)
+                                const MK undecodable = mand(neq_u(or_u(dfl, dfl1), zero_u<V>()), mnot(mand(f_is, lt_u(f_entry, (unsigned)ROW_K))));
+                                const MK rows_ok = eq_u(quad_sum_u(mbit(undecodable)), zero_u<V>());
+                                fast_env = mand(mand(unconverged, fac_valid), mand(mand(one_flip, xh_same), rows_ok));
+                                if (LS || !o.rank_one) fast_env = lt(V(1), V(0));      // (the line-searched iteration works on full passes)
+                                full = any_lane(mand(unconverged, mnot(fast_env))) ? 1u : 0u;
+                                if (!LS && any_lane(fast_env)) {
+                                    W fyr[3];
+                                    V fyl[2], fym;
+                                    if (o.lean) { fac_load(sc, fac); if (PAIR) fac_load_cx(sc, fac); }
+                                    rank_one_pass<V, PAIR>(sc, fac, dk, m.c[LM_MU], f_entry, f_is, f_plus, f_tan2, f_on, yr, yl, ym, fyr, fyl, fym);
+#pragma unroll
+                                    for (int ip = 0; ip < 3; ip++) yr[ip] = selw(fast_env, fyr[ip], yr[ip]);
+                                    yl[0] = sel(fast_env, fyl[0], yl[0]); yl[1] = sel(fast_env, fyl[1], yl[1]); ym = sel(fast_env, fym, ym);
+#ifdef JB_WAVE_STATS
+                                    s.st_fast = s.st_fast + V(1);
+#endif
+                                }
+                                prev_bw0 = acc.bw0; prev_bw1 = acc.bw1; prev_xh = acc.xh;      // the sets the new iterates are solved for
+                            }
+                        }
+                        {
+                            const unsigned f = wave_bcast_u(fin);
+                            final_pass = f != 0u;
+                            wave_capped = f == 2u;
+                        }
+                        full_pass = wave_bcast_u(full) != 0u;
                     }
-                    {
-                        const unsigned f = wave_bcast_u(fin);
-                        final_pass = f != 0u;
-                        wave_capped = f == 2u;
-                    }
-                    full_pass = wave_bcast_u(full) != 0u;
                     JB_PROF_ADD(o, 7);
                     if (final_pass || full_pass) break;
                     if (is_main) {      // rank-one passes only: their iterates go to the scratch for the next check
@@ -2915,15 +2964,19 @@ JB_HD bool substep(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>
 #endif
     if (o.lean && sc.grp == 0) state_load(sc, s);       // LEAN: the state lives in the scratch between substeps
     const bool rep = sc.grp == 0 || (o.offload && sc.grp == 1);      // main lanes and their replica (SimOpts::offload)
-    if (rep || (o.aux && sc.grp >= 2)) Rw = quat2mat(s.qw, s.qx, s.qy, s.qz);      // (every lane that holds the root state) the quaternion is kept normalised: normalise_state() once per kernel, phase C after every substep
-    if (o.contacts && rep) {
+    // Scalar votes: every lane runs the broadphase on whatever state it holds (a helper lane's harmless one) and the MAIN lanes' votes decide
+    // (main_vote) - `xt` stays in scalar registers.  Otherwise the main lanes and their replica vote and the first lane's answer is fetched.
+    const bool sv = o.scalar_votes != 0;
+    if (sv || rep || (o.aux && sc.grp >= 2)) Rw = quat2mat(s.qw, s.qx, s.qy, s.qz);      // (every lane that holds the root state; scalar votes: every lane) the quaternion is kept normalised: normalise_state() once per kernel, phase C after every substep
+    auto vote = [&](const auto& mk) { return sv ? main_vote(sc, mk) : any_lane(mk); };
+    if (o.contacts && (sv || rep)) {
         const Vec3<V> nb = v3<V>(Rw.m[6], Rw.m[7], Rw.m[8]);         // floor normal in root coordinates
         // upper leg: sphere around the upper cylinder (+ slack for the shoulder angle)
         auto near_leg = mor(lt(s.pz + dot(ldv3(m, LM_BS_LEG_C), nb), m.c[LM_BS_LEG_R]), gt(vabs(s.th1), V(0.3)));
         // the lane's root / motor-body geoms: a bounding sphere first (at rest it clears the floor by 8 mm or more), and only
         // when some lane's sphere reaches the floor the two oriented boxes (support function of a box along -n)
         auto near_body = lt(s.pz + dot(ldv3(m, LM_BS_BODY_C), nb), m.c[LM_BS_BODY_R]);
-        if (any_lane(near_body)) {
+        if (vote(near_body)) {
             near_body = lt(V(1), V(0));
 #pragma unroll
             for (int k = 0; k < 2; k++) {
@@ -2933,9 +2986,9 @@ JB_HD bool substep(const LaneModel<V>& m, const LaneScratch<V>& sc, LaneState<V>
                 near_body = mor(near_body, lt(s.pz + dot(ldv3(m, b), nb), sup));
             }
         }
-        xt = (any_lane(near_leg) ? 1u : 0u) | (any_lane(near_body) ? 2u : 0u);
+        xt = (vote(near_leg) ? 1u : 0u) | (vote(near_body) ? 2u : 0u);
     }
-    xt = wave_bcast_u(xt);      // helper groups follow the main lanes' decision
+    if (!sv) xt = wave_bcast_u(xt);      // helper groups follow the main lanes' decision
     bool xtra = xt != 0u;
     const bool xbody = (xt & 2u) != 0u;
 #ifdef JB_NO_XTRA

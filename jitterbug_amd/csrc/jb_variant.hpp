@@ -33,6 +33,13 @@ struct StepLayout {
                              // adds scratch operations to their substep loop's hot part: tools/asm_spills.py).  Same bits either way.
     bool every_lane_update;  // the iterate's update after star_solve is made by every lane, not under the main lanes' predicate (SimOpts::every_lane_update,
                              // tools/experiments/group_liveness.txt); false: the two rows whose hot part it would give scratch operations.  Same bits.
+    bool scalar_votes;       // the wave-uniform decisions of the Newton loop's check and of the substep's broadphase are votes of the main lanes taken by every
+                             // lane (jb_lane.hpp main_vote, SimOpts::scalar_votes, tools/experiments/scalar_votes.txt); false: under the main lanes'
+                             // predicate and fetched back from the first lane - the rows that would gain a hot scratch operation or lose occupancy,
+                             // and every row with -DJB_VECTOR_VOTES (today no row objects).  Same bits.
+    bool late_env_index;     // the kernel's closing stores form their addresses from a fresh copy of the env index, so that no byte offset of the
+                             // entry's loads stays in registers through the loops (jb_api.hip step_body); it comes with the scalar votes - whose
+                             // flagship row would otherwise spill that offset once per launch - except on the one row it gives hot scratch operations
 };
 
 constexpr StepLayout step_layout(int epw, bool lean, bool pair) {
@@ -53,6 +60,12 @@ constexpr StepLayout step_layout(int epw, bool lean, bool pair) {
     l.waves_per_simd = lean ? 2 : 1;
     l.fused_row_build = !(lean && pair) && !(pair && epw == 1) && !(!pair && !lean && epw == 8);
     l.every_lane_update = !(lean && !pair && epw == 2) && !(!pair && !lean && epw == 8);
+#ifdef JB_VECTOR_VOTES
+    l.scalar_votes = false;
+#else
+    l.scalar_votes = true;
+#endif
+    l.late_env_index = l.scalar_votes && !(pair && !lean && epw == 8);
     return l;
 }
 
@@ -126,7 +139,7 @@ JB_HD SimOpts sim_opts(const StepLayout& l, int contacts, int max_newton, int im
     SimOpts o;
     o.contacts = contacts; o.max_newton = max_newton; o.implicit_damp = implicit_damp; o.rank_one = rank_one; o.spread = spread;
     o.lean = l.lean ? 1 : 0; o.offload = l.offload ? 1 : 0; o.aux = l.aux ? 1 : 0; o.fuse_rows = l.fused_row_build ? 1 : 0;
-    o.every_lane_update = l.every_lane_update ? 1 : 0;
+    o.every_lane_update = l.every_lane_update ? 1 : 0; o.scalar_votes = l.scalar_votes ? 1 : 0;
     o.prof = nullptr; o.hist = nullptr;
     return o;
 }
