@@ -44,7 +44,7 @@
 #define JB_P_GAIN        13   /* gainprm[0] jitterbug.xml:141 */
 #define JB_P_BIASPRM     14   /* 3: jitterbug.xml:144 */
 #define JB_P_CTRLRANGE   17   /* 2: jitterbug.xml:133 */
-#define JB_P_ROOTPOS0    19   /* 3: world position of the root body at qpos0 */
+#define JB_P_ROOTPOS0    19   /* 3: world position of the root body at qpos0 (x = y = 0: the kernels keep the height alone, another table is JB_E_MODEL) */
 #define JB_P_TARGETZ     22   /* world z of the target geom, jitterbug.xml:115 */
 #define JB_P_IMPRATIO    23
 #define JB_OPT_SIZE      24

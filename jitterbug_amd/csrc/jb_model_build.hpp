@@ -40,6 +40,7 @@ template <typename T> JB_HD int build_lane_model(const double* P, int leg, T* ou
     for (int b = 0; b < JB_NBODY; b++) mtot += body(b)[JB_B_MASS];
     out[LM_MTOT] = T(mtot);
     out[LM_TARGET_Z] = T(P[JB_P_TARGETZ]); out[LM_ROOT_Z0] = T(P[JB_P_ROOTPOS0 + 2]);
+    if (P[JB_P_ROOTPOS0] != 0.0 || P[JB_P_ROOTPOS0 + 1] != 0.0) return -7;      // an episode starts at x = y = 0 (jb_task.hpp episode_reset): only the height is kept
 
     // root body
     out[LM_M0] = T(body(0)[JB_B_MASS]); put3(LM_C0, body(0) + JB_B_COM);

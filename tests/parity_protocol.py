@@ -139,11 +139,11 @@ class ParityTally:
     """The protocol's counters over a run of env-steps, whoever drives the envs (teacher_forced and free_running below).
     add() takes one compared control step - the oracle env just stepped, the GPU's and the oracle's
     observations and rewards, and the GPU's post-step state (q, v, target) of the compared envs - and returns the env-steps of the near-switch
-    class that left the tolerance (those the cascade check follows); cascade() takes the GPU's NEXT step of such envs from its own state
+    class that left the tolerance (those the cascade check follows; sel: a bool mask of the envs compared in this step, where not all are); cascade() takes the GPU's NEXT step of such envs from its own state
     against the oracle's from that same state; result() the figures.  task, P: what the rewards are the rewards of (P [NPARAM] or [n, NPARAM])."""
 
     def __init__(self, n, task, P, contacts=True):
-        self.n, self.contacts, self.steps = n, contacts, 0
+        self.n, self.contacts, self.steps, self.env_steps = n, contacts, 0, 0
         self.task, self.P = task, np.asarray(P, dtype=np.float64)
         self.reward_bad, self.worst_reward_own, self.worst_reward_ratio = 0, 0.0, 0.0
         self.tot = self.ok = self.okr = self.big = 0
@@ -153,13 +153,25 @@ class ParityTally:
         self.worst_clamped = self.worst_deep_converged = 0.0
         self.worst = self.worst_well = self.worst_ill = self.worst_deep = self.flip_margin_max = self.worst_reward_held = 0.0
 
-    def add(self, o, og, oo, rg, ro, gstate):
+    def add(self, o, og, oo, rg, ro, gstate, sel=None):
+        if sel is not None:          # only the envs of this bool mask are compared (a run across episode boundaries leaves out the env-steps that end in a reset)
+            return self._add_selected(o, og, oo, rg, ro, gstate, np.asarray(sel, dtype=bool))
+        return self._add(classify(o, self.contacts), unconverged(o, self.contacts), o.conditioning()["switch"] if self.contacts else None, self.P, og, oo, rg, ro, gstate)
+
+    def _add_selected(self, o, og, oo, rg, ro, gstate, sel):
+        out = np.zeros(self.n, bool)
+        if sel.any():
+            out[sel] = self._add(tuple(c[sel] for c in classify(o, self.contacts)), unconverged(o, self.contacts)[sel], o.conditioning()["switch"][sel] if self.contacts else None,
+                                 self.P[sel] if self.P.ndim == 2 else self.P, og[sel], oo[sel], rg[sel], ro[sel], tuple(x[sel] for x in gstate))
+        return out
+
+    def _add(self, classes, unconv, switch, P, og, oo, rg, ro, gstate):
         from tests import task_reference as tr
-        well, deep, near = classify(o, self.contacts)
+        well, deep, near = classes
         qg, vg, tg = gstate
-        Pi = (lambda i: self.P[i]) if self.P.ndim == 2 else (lambda i: self.P)
-        own = np.abs(rg.astype(np.float64) - np.array([O.reward(Pi(i), self.task, qg[i], vg[i], tg[i]) for i in range(self.n)]))
-        rb = tr.reward_bound(self.P, self.task, qg, vg, tg)
+        Pi = (lambda i: P[i]) if P.ndim == 2 else (lambda i: P)
+        own = np.abs(rg.astype(np.float64) - np.array([O.reward(Pi(i), self.task, qg[i], vg[i], tg[i]) for i in range(len(rg))]))
+        rb = tr.reward_bound(P, self.task, qg, vg, tg)
         self.reward_bad += int((own > rb).sum())          # (a non-finite reward counts: the comparison is False only inside the bound)
         self.reward_bad += int((~np.isfinite(own)).sum())
         self.worst_reward_own = max(self.worst_reward_own, float(own.max()))
@@ -167,7 +179,7 @@ class ParityTally:
         og = og.astype(np.float64)
         w = within(og, oo)
         err = np.abs(og - oo)
-        self.steps += 1
+        self.steps += 1; self.env_steps += len(rg)
         self.ok += w.sum(); self.tot += w.size
         self.okr += within(rg.astype(np.float64), ro).sum()
         self.big += (err > 1e-2).sum()
@@ -177,17 +189,17 @@ class ParityTally:
         viol = strict.any(axis=1)              # env-steps with an entry outside the strict tolerance, whatever their class
         self.strict_bad += int(strict[well].sum())
         self.far_off += int((err > 1e-3 * np.abs(oo) + 1e-5).any(axis=1).sum())
-        flipped = viol & ~(deep & unconverged(o, self.contacts))          # (what leaves the tolerance in the unconverged part of the deep class is no flip: DEEP_ERROR_CAP)
+        flipped = viol & ~(deep & unconv)          # (what leaves the tolerance in the unconverged part of the deep class is no flip: DEEP_ERROR_CAP)
         if self.contacts and flipped.any():
-            self.flip_margin_max = max(self.flip_margin_max, float(o.conditioning()["switch"][flipped].max()))      # the LARGEST contact-switch margin at which fp32 still flipped: what MARGIN_TOL must cover
+            self.flip_margin_max = max(self.flip_margin_max, float(switch[flipped].max()))      # the LARGEST contact-switch margin at which fp32 still flipped: what MARGIN_TOL must cover
         if well.any():
             self.worst_well = max(self.worst_well, err[well].max())
-            self.unconverged_well += int((well & unconverged(o, self.contacts)).sum())
+            self.unconverged_well += int((well & unconv).sum())
         if deep.any():
             self.deep_steps += int(deep.sum()); self.deep_bad += int((~w[deep]).sum())
             self.deep_strict_bad += int(strict[deep].sum())
             self.worst_deep = max(self.worst_deep, float(err[deep].max()))
-            cl = deep & unconverged(o, self.contacts)
+            cl = deep & unconv
             self.clamped_steps += int(cl.sum()); self.clamped_strict_bad += int(strict[cl].sum())
             if cl.any():
                 self.worst_clamped = max(self.worst_clamped, float(err[cl].max()))
@@ -208,7 +220,7 @@ class ParityTally:
             self.cascade_bad += int((~strict_within(og2.astype(np.float64)[sel], oo2[sel]).all(axis=1)).sum())
 
     def result(self, cap, **extra):
-        env_steps = self.n * self.steps
+        env_steps = self.env_steps          # (n x steps, unless add() was given a selection)
         return dict(well_bad=int(self.well_tot - self.well_ok), frac=self.ok / self.tot, worst=self.worst, frac_reward=self.okr / env_steps, cap=float(cap), frac_big=self.big / self.tot,
                     well_frac=self.well_ok / max(self.well_tot, 1), well_big=int(self.well_big), worst_well=self.worst_well,
                     ill_frac=self.ill_steps / env_steps, ill_steps=int(self.ill_steps), ill_bad_steps=int(self.ill_bad_steps),

@@ -441,6 +441,11 @@ def test_edge_cases_batch_sizes_and_layouts():
     bad = P.copy(); bad[model.P_SOLIMP + 4] = 3.0            # solimp power != 2 is not implemented by the kernel
     with pytest.raises(_lib.JitterbugHipError, match="JB_E_MODEL"):
         g.set_model_params(bad)
+    for k in (0, 1):                                         # an episode that starts off the origin: the kernel's reset keeps the height alone
+        bad = P.copy(); bad[model.P_ROOTPOS0 + k] = 1e-3
+        with pytest.raises(_lib.JitterbugHipError, match=r"JB_E_MODEL.*code -7"):
+            g.set_model_params(bad)
+    assert np.isfinite(g.step(np.zeros(4, dtype=np.float32))[0]).all()      # (the handle keeps the model it had)
     g.close()
 
 
