@@ -468,92 +468,118 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // and wave operations; its rows are never copied out).  The main lanes then reload the untouched input state, run fw_lane and write their rows
 // into an LDS image of the block's part of each output array (the scratch is dead by then); the wave copies each present image out as one
 // contiguous segment, in 16-byte words where the segment starts on one.  Nothing but the outputs is written.
-struct FwArgs {
+// What both substep passes are told about their launch (jb_forward_device / jb_contacts_device fill it in prepare_pass).
+struct PassArgs {
     SnapView first;              // snapshot 0 (or the handle's blocks)
     long long stride_words;      // distance between consecutive snapshots, in 4-byte words
     int waves_per_snap;          // ceil(N / 4)
     const float* ctrl;           // nullable [n_snaps * N]: the action of every env-state (NULL: 0)
-    float *qacc, *qfrc, *bacc, *motor; unsigned char* unconv;      // each nullable
+    unsigned char* unconv;       // nullable [n_snaps * N]
+};
+struct FwArgs {
+    PassArgs p;
+    float *qacc, *qfrc, *bacc, *motor;      // each nullable
 };
 constexpr int FW_EPW = 4;
+// A pass's wave up to its substep: everything step_body does before the first substep of a control step, on the state of env-state
+// (k, env) instead of the handle's.  BOTH pass kernels run this one text, which is what makes the contact pass's solve the forward pass's.
+// (It names the dynamic LDS itself: handing the pointer in changes the code of the STEP kernels - DESIGN.md, "module coupling".)
+template <bool PAIR>
+struct PassWave {
+    int grp, quad, leg, k, lblock, env;
+    bool rep;                    // this lane group holds the state
+    LaneModel<float> m;
+    LaneScratch<float> scr;
+    LaneState<float> s;
+    SnapView v;                  // the snapshot of this wave
+    float ctrl;
+    SimOpts o;
+    __device__ __forceinline__ void begin(const KArgs& a, const PassArgs& f) {
+        extern __shared__ float lds[];           // [SC_COUNT][16] per-lane scratch, then the lane constant table(s): step_body's layout
+        constexpr StepLayout LAY = step_layout(FW_EPW, false, PAIR);
+        constexpr int MAIN = LAY.main_lanes, SCN = LAY.scratch_floats;
+        static_assert(LAY.groups * MAIN == 64 && LAY.offload && LAY.red_lds && !LAY.split_tables && LAY.ovc_floats == 0, "the one-wave-per-SIMD layout at four envs per wave fills the wave");
+        const int lane_in_grp = threadIdx.x % MAIN;
+        grp = threadIdx.x / MAIN; quad = lane_in_grp >> 2; leg = threadIdx.x & 3;
+        k = (int)blockIdx.x / f.waves_per_snap; lblock = (int)blockIdx.x - k * f.waves_per_snap;
+        stage_model<false>(a, lds + SCN * MAIN, lblock, quad, leg, m, false, LAY.pair_entries, LAY.aux ? grp : -1);      // (a.epw == FW_EPW: prepare_pass)
+        env = lblock * FW_EPW + quad;
+        if (env >= a.n) env = a.n - 1;
+        scr.p = lds + lane_in_grp;
+        scr.stride = MAIN;
+        scr.grp = grp; scr.ngrp = LAY.groups; scr.gstride = MAIN;
+        scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds;
+        scr.ovc_stride = MAIN;
+        scr.pd = LAY.pd;
+        scr.aux_lane = LAY.aux && grp >= 2;
+        v = f.first;
+        v.root += (long long)k * f.stride_words; v.leg += (long long)k * f.stride_words;
+        rep = holds_state(LAY, grp);
+        if (rep) {
+            KArgs av;                 // the fields load_state reads
+            av.n = a.n; av.root = (float*)v.root; av.leg = (float*)v.leg;
+            load_state(av, env, env * 4 + leg, s);
+        } else helper_lane_state(s);
+        s.fail = 0.f;                 // counts this substep alone
+#ifdef JB_WAVE_STATS
+        s.st_xtra = 0.f; s.st_sweeps = 0.f; s.st_contact = 0.f; s.st_slots = 0.f; s.st_fast = 0.f; s.st_checks = 0.f;
+#endif
+        o = sim_opts(LAY, a.contacts, a.max_newton, 1, a.rank_one, a.spread);
+        if (grp == 0) {
+#pragma unroll
+            for (int i = 0; i < 56; i++) scr.st(SC_ZERO + i, 0.f);
+        }
+        ctrl = 0.f;
+        if (rep && f.ctrl) ctrl = f.ctrl[(size_t)k * a.n + env];
+        if (rep) normalise_state(s);
+        if (PAIR && rep) scr.st(scr.pd + 11, 0.f);      // the narrow phase starts cold, as in the first substep of a control step
+    }
+    // this lane's env-state is a real one (not the repeat that fills a ragged last quad) and the lane speaks for it
+    __device__ __forceinline__ bool speaks(const KArgs& a) const { return leg == 0 && lblock * FW_EPW + quad < a.n; }
+    __device__ __forceinline__ size_t env_state(const KArgs& a) const { return (size_t)k * a.n + env; }
+    // the wave copies the block's LDS image of one output array (len floats per env-state) out as one contiguous segment, if the array is wanted
+    __device__ __forceinline__ void store(const KArgs& a, float* arr, const float* image, int len) const {
+        if (!arr) return;
+        const int left = a.n - lblock * FW_EPW, n_es = left < FW_EPW ? left : FW_EPW;
+        float* dst = arr + ((size_t)k * a.n + (size_t)lblock * FW_EPW) * len;
+        ro_store_segment(dst, image, n_es * len, (((uintptr_t)dst) & 15u) == 0 ? 1 : 0, (int)threadIdx.x);
+    }
+};
 constexpr int FW_LDS_QACC = 0, FW_LDS_QFRC = FW_LDS_QACC + FW_EPW * FW_NV, FW_LDS_BACC = FW_LDS_QFRC + FW_EPW * FW_NV, FW_LDS_MOTOR = FW_LDS_BACC + FW_EPW * FW_BACC,
               FW_LDS_FLOATS = FW_LDS_MOTOR + FW_EPW * FW_MOTOR;
 static_assert(FW_LDS_QFRC % 4 == 0 && FW_LDS_BACC % 4 == 0 && FW_LDS_MOTOR % 4 == 0, "every LDS image starts on a 16-byte word");
 static_assert(FW_LDS_FLOATS <= SC_COUNT * 4 * FW_EPW, "the images fit into the (dead) scratch");
 template <bool PAIR>
 __global__ __launch_bounds__(64) void jb_forward_kernel(KArgs a, FwArgs f) {
-    extern __shared__ float lds[];           // [SC_COUNT][16] per-lane scratch, then the lane constant table(s): step_body's layout
-    constexpr StepLayout LAY = step_layout(FW_EPW, false, PAIR);
-    constexpr int MAIN = LAY.main_lanes, SCN = LAY.scratch_floats;
-    static_assert(LAY.groups * MAIN == 64 && LAY.offload && LAY.red_lds && !LAY.split_tables && LAY.ovc_floats == 0, "the one-wave-per-SIMD layout at four envs per wave fills the wave");
-    const int lane_in_grp = threadIdx.x % MAIN, grp = threadIdx.x / MAIN, quad = lane_in_grp >> 2, leg = threadIdx.x & 3;
-    const int k = (int)blockIdx.x / f.waves_per_snap, lblock = (int)blockIdx.x - k * f.waves_per_snap;
-    LaneModel<float> m;
-    stage_model<false>(a, lds + SCN * MAIN, lblock, quad, leg, m, false, LAY.pair_entries, LAY.aux ? grp : -1);      // (a.epw == FW_EPW: jb_forward_device)
-    int env = lblock * FW_EPW + quad;
-    if (env >= a.n) env = a.n - 1;
-    LaneScratch<float> scr;
-    scr.p = lds + lane_in_grp;
-    scr.stride = MAIN;
-    scr.grp = grp; scr.ngrp = LAY.groups; scr.gstride = MAIN;
-    scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds;
-    scr.ovc_stride = MAIN;
-    scr.pd = LAY.pd;
-    scr.aux_lane = LAY.aux && grp >= 2;
-    SnapView v = f.first;
-    v.root += (long long)k * f.stride_words; v.leg += (long long)k * f.stride_words;
-    const bool rep = holds_state(LAY, grp);
-    LaneState<float> s;
-    if (rep) {
-        KArgs av;                 // the fields load_state reads
-        av.n = a.n; av.root = (float*)v.root; av.leg = (float*)v.leg;
-        load_state(av, env, env * 4 + leg, s);
-    } else helper_lane_state(s);
-    s.fail = 0.f;                 // counts this substep alone
-#ifdef JB_WAVE_STATS
-    s.st_xtra = 0.f; s.st_sweeps = 0.f; s.st_contact = 0.f; s.st_slots = 0.f; s.st_fast = 0.f; s.st_checks = 0.f;
-#endif
-    const SimOpts o = sim_opts(LAY, a.contacts, a.max_newton, 1, a.rank_one, a.spread);
-    if (grp == 0) {
-#pragma unroll
-        for (int i = 0; i < 56; i++) scr.st(SC_ZERO + i, 0.f);
-    }
-    float ctrl = 0.f;
-    if (rep && f.ctrl) ctrl = f.ctrl[(size_t)k * a.n + env];
-    if (rep) normalise_state(s);
-    if (PAIR && rep) scr.st(scr.pd + 11, 0.f);      // the narrow phase starts cold, as in the first substep of a control step
-    (void)substep<float, PAIR>(m, scr, s, ctrl, o);
+    extern __shared__ float lds[];
+    PassWave<PAIR> w;
+    w.begin(a, f.p);
+    (void)substep<float, PAIR>(w.m, w.scr, w.s, w.ctrl, w.o);
     __syncthreads();                                // every lane group is done with the scratch: it becomes the output images
-    if (grp == 0) {
-        const FwState<float> st = fw_load<float>(v, env, leg);
+    if (w.grp == 0) {
+        const int quad = w.quad, leg = w.leg;
+        const FwState<float> st = fw_load<float>(w.v, w.env, leg);
         FwAcc<float> y;
 #pragma unroll
-        for (int i = 0; i < 3; i++) { y.lin[i] = s.wl[i]; y.ang[i] = s.wa[i]; }
-        y.j1 = s.wj[0]; y.j2 = s.wj[1]; y.m = s.wm;
+        for (int i = 0; i < 3; i++) { y.lin[i] = w.s.wl[i]; y.ang[i] = w.s.wa[i]; }
+        y.j1 = w.s.wj[0]; y.j2 = w.s.wj[1]; y.m = w.s.wm;
         FwOut<float> out;
         out.qacc = f.qacc ? lds + FW_LDS_QACC + quad * FW_NV : nullptr;
         out.qfrc = f.qfrc ? lds + FW_LDS_QFRC + quad * FW_NV : nullptr;
         out.bacc = f.bacc ? lds + FW_LDS_BACC + quad * FW_BACC : nullptr;
         out.motor = f.motor ? lds + FW_LDS_MOTOR + quad * FW_MOTOR : nullptr;
         float p[6];
-        fw_lane<float>(st, y, ctrl, m.c.inv, leg, out, p);
+        fw_lane<float>(st, y, w.ctrl, w.m.c.inv, leg, out, p);
         if (out.qfrc) {
 #pragma unroll
             for (int i = 0; i < 6; i++) { const float t = quad_sum(p[i]); if (leg == (i & 3)) out.qfrc[i] = t; }
         }
-        if (f.unconv && leg == 0 && lblock * FW_EPW + quad < a.n) f.unconv[(size_t)k * a.n + env] = s.fail > 0.f ? 1 : 0;
+        if (f.p.unconv && w.speaks(a)) f.p.unconv[w.env_state(a)] = w.s.fail > 0.f ? 1 : 0;
     }
     __syncthreads();
-    const int left = a.n - lblock * FW_EPW, n_es = left < FW_EPW ? left : FW_EPW, tid = threadIdx.x;
-    const size_t es0 = (size_t)k * a.n + (size_t)lblock * FW_EPW;
-    auto store = [&](float* arr, int at, int len) {
-        if (!arr) return;
-        float* dst = arr + es0 * len;
-        ro_store_segment(dst, lds + at, n_es * len, (((uintptr_t)dst) & 15u) == 0 ? 1 : 0, tid);
-    };
-    store(f.qacc, FW_LDS_QACC, FW_NV); store(f.qfrc, FW_LDS_QFRC, FW_NV); store(f.bacc, FW_LDS_BACC, FW_BACC); store(f.motor, FW_LDS_MOTOR, FW_MOTOR);
+    w.store(a, f.qacc, lds + FW_LDS_QACC, FW_NV); w.store(a, f.qfrc, lds + FW_LDS_QFRC, FW_NV);
+    w.store(a, f.bacc, lds + FW_LDS_BACC, FW_BACC); w.store(a, f.motor, lds + FW_LDS_MOTOR, FW_MOTOR);
 }
-
 // ---------------------------------------------------------------------------------------------- contacts (jb_contacts.hpp)
 // The forward pass's wave, launch shape and substep - step_layout(4, false, PAIR), n_snaps x ceil(N / 4) workgroups, a ragged last quad
 // repeats its last env - so the solve behind the forces is the one behind jb_forward_kernel's qacc, bit for bit.  The substep is handed a
@@ -563,68 +589,29 @@ __global__ __launch_bounds__(64) void jb_forward_kernel(KArgs a, FwArgs f) {
 // (ct_slot) and a lane that can hold a contact there writes its row, adds a floor row's force to its geom's three words - every geom belongs
 // to one lane, no exchange - and counts.  The wave copies each present image out as one contiguous segment.  Nothing but the outputs is written.
 struct CtArgs {
-    SnapView first;              // snapshot 0 (or the handle's blocks)
-    long long stride_words;      // distance between consecutive snapshots, in 4-byte words
-    int waves_per_snap;          // ceil(N / 4)
+    PassArgs p;
     int img;                     // where the images start in the dynamic LDS, in floats (a multiple of 4: behind the scratch and the tables)
-    const float* ctrl;           // nullable [n_snaps * N]
-    float *contact, *geom_frc; int* ncon; unsigned char* unconv;      // each nullable
+    float *contact, *geom_frc; int* ncon;      // each nullable
 };
 constexpr int CT_LDS_TABLE = 0, CT_LDS_GEOM = CT_LDS_TABLE + FW_EPW * CT_TABLE, CT_LDS_FLOATS = CT_LDS_GEOM + FW_EPW * CT_GEOMF;
 static_assert(CT_LDS_GEOM % 4 == 0 && CT_LDS_FLOATS % 4 == 0 && CT_TABLE % 4 == 0 && (FW_EPW * CT_GEOMF) % 4 == 0, "every LDS image starts on a 16-byte word and a full block's segment is whole words");
 template <bool PAIR>
 __global__ __launch_bounds__(64) void jb_contacts_kernel(KArgs a, CtArgs f) {
-    extern __shared__ float lds[];           // [SC_COUNT][16] per-lane scratch, the lane constant table(s), then the output images
-    constexpr StepLayout LAY = step_layout(FW_EPW, false, PAIR);
-    constexpr int MAIN = LAY.main_lanes, SCN = LAY.scratch_floats;
-    static_assert(LAY.groups * MAIN == 64 && LAY.offload && LAY.red_lds && !LAY.split_tables && LAY.ovc_floats == 0, "the one-wave-per-SIMD layout at four envs per wave fills the wave");
-    const int lane_in_grp = threadIdx.x % MAIN, grp = threadIdx.x / MAIN, quad = lane_in_grp >> 2, leg = threadIdx.x & 3, tid = threadIdx.x;
-    const int k = (int)blockIdx.x / f.waves_per_snap, lblock = (int)blockIdx.x - k * f.waves_per_snap;
+    extern __shared__ float lds[];           // PassWave's scratch and tables, then the output images
     float* const img = lds + f.img;
-    for (int i = tid; i < CT_LDS_FLOATS / 4; i += 64) ((float4*)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);      // an inactive row is all zeros
-    LaneModel<float> m;
-    stage_model<false>(a, lds + SCN * MAIN, lblock, quad, leg, m, false, LAY.pair_entries, LAY.aux ? grp : -1);      // (a.epw == FW_EPW: jb_contacts_device)
-    int env = lblock * FW_EPW + quad;
-    if (env >= a.n) env = a.n - 1;
-    LaneScratch<float> scr;
-    scr.p = lds + lane_in_grp;
-    scr.stride = MAIN;
-    scr.grp = grp; scr.ngrp = LAY.groups; scr.gstride = MAIN;
-    scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds;
-    scr.ovc_stride = MAIN;
-    scr.pd = LAY.pd;
-    scr.aux_lane = LAY.aux && grp >= 2;
-    SnapView v = f.first;
-    v.root += (long long)k * f.stride_words; v.leg += (long long)k * f.stride_words;
-    const bool rep = holds_state(LAY, grp);
-    LaneState<float> s;
-    if (rep) {
-        KArgs av;                 // the fields load_state reads
-        av.n = a.n; av.root = (float*)v.root; av.leg = (float*)v.leg;
-        load_state(av, env, env * 4 + leg, s);
-    } else helper_lane_state(s);
-    s.fail = 0.f;                 // counts this substep alone
-#ifdef JB_WAVE_STATS
-    s.st_xtra = 0.f; s.st_sweeps = 0.f; s.st_contact = 0.f; s.st_slots = 0.f; s.st_fast = 0.f; s.st_checks = 0.f;
-#endif
-    const SimOpts o = sim_opts(LAY, a.contacts, a.max_newton, 1, a.rank_one, a.spread);
-    if (grp == 0) {
-#pragma unroll
-        for (int i = 0; i < 56; i++) scr.st(SC_ZERO + i, 0.f);
-    }
-    float ctrl = 0.f;
-    if (rep && f.ctrl) ctrl = f.ctrl[(size_t)k * a.n + env];
-    if (rep) normalise_state(s);
-    if (PAIR && rep) scr.st(scr.pd + 11, 0.f);      // the narrow phase starts cold, as in the first substep of a control step
+    for (int i = threadIdx.x; i < CT_LDS_FLOATS / 4; i += 64) ((float4*)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);      // an inactive row is all zeros
+    PassWave<PAIR> w;
+    w.begin(a, f.p);
     CtTap<float> tap;
-    (void)substep<float, PAIR, SolveTap<float>>(m, scr, s, ctrl, o, tap.tap());
+    (void)substep<float, PAIR, SolveTap<float>>(w.m, w.scr, w.s, w.ctrl, w.o, tap.tap());
     const unsigned live = tap.live;
     __syncthreads();                                // the solve's last scratch writes, and the zeroed images
-    if (grp == 0) {
-        const RoState<float> st = ro_load<float>(v, env, leg);
+    if (w.grp == 0) {
+        const int quad = w.quad, leg = w.leg;
+        const RoState<float> st = ro_load<float>(w.v, w.env, leg);
         CtPose<float> P;
         P.R = ro_quat2mat(st.q, st.ql); P.px = st.px; P.py = st.py; P.pz = st.pz; P.pz_lo = st.pz_lo;
-        const CtY<float> y = ct_y<float>(scr, tap);
+        const CtY<float> y = ct_y<float>(w.scr, tap);
         float* const rows = f.contact ? img + CT_LDS_TABLE + quad * CT_TABLE : nullptr;
         float* const gfrc = f.geom_frc ? img + CT_LDS_GEOM + quad * CT_GEOMF : nullptr;
         unsigned count = 0u;
@@ -632,7 +619,7 @@ __global__ __launch_bounds__(64) void jb_contacts_kernel(KArgs a, CtArgs f) {
         for (unsigned rest = live; rest; rest &= rest - 1u) {
             const int slot = __builtin_ctz(rest);
             CtRowOut<float> r;
-            ct_slot<float, PAIR>(m, scr, live, slot, P, y, r);
+            ct_slot<float, PAIR>(w.m, w.scr, live, slot, P, y, r);
             if (ct_has_row(leg, slot)) {
                 if (rows) {
                     float* q = rows + ct_row(leg, slot) * CT_W;
@@ -647,19 +634,11 @@ __global__ __launch_bounds__(64) void jb_contacts_kernel(KArgs a, CtArgs f) {
             }
         }
         count = quad_sum_u(count);
-        const bool real = lblock * FW_EPW + quad < a.n && leg == 0;
-        if (f.ncon && real) f.ncon[(size_t)k * a.n + env] = (int)count;
-        if (f.unconv && real) f.unconv[(size_t)k * a.n + env] = s.fail > 0.f ? 1 : 0;
+        if (f.ncon && w.speaks(a)) f.ncon[w.env_state(a)] = (int)count;
+        if (f.p.unconv && w.speaks(a)) f.p.unconv[w.env_state(a)] = w.s.fail > 0.f ? 1 : 0;
     }
     __syncthreads();
-    const int left = a.n - lblock * FW_EPW, n_es = left < FW_EPW ? left : FW_EPW;
-    const size_t es0 = (size_t)k * a.n + (size_t)lblock * FW_EPW;
-    auto store = [&](float* arr, int at, int len) {
-        if (!arr) return;
-        float* dst = arr + es0 * len;
-        ro_store_segment(dst, img + at, n_es * len, (((uintptr_t)dst) & 15u) == 0 ? 1 : 0, tid);
-    };
-    store(f.contact, CT_LDS_TABLE, CT_TABLE); store(f.geom_frc, CT_LDS_GEOM, CT_GEOMF);
+    w.store(a, f.contact, img + CT_LDS_TABLE, CT_TABLE); w.store(a, f.geom_frc, img + CT_LDS_GEOM, CT_GEOMF);
 }
 
 // Self-check of the kernarg-segment reads above, run once per process before the first handle is handed out: a kernel with the step kernels'
@@ -1102,25 +1081,16 @@ template <int... I> static const StepKernel* step_kernels(std::integer_sequence<
     static const StepKernel table[] = {step_row_kernel<I>()...};      // by row of STEP_ROWS
     return table;
 }
-// ... and the forward pass of a handle (jb_forward_kernel), by whether its step kernel has the pair contacts
-typedef void (*ForwardKernel)(KArgs, FwArgs);
-template <bool PAIR> static ForwardKernel forward_kernel() {
+// ... and a substep pass of a handle (jb_forward_kernel for FwArgs, jb_contacts_kernel for CtArgs), by whether its step kernel has the pair contacts
+template <typename Args> using PassKernel = void (*)(KArgs, Args);
+template <typename Args, bool PAIR> static PassKernel<Args> pass_kernel() {
 #ifdef JB_DEV_ONLY4      // development builds: the ordinary layout only, like the step kernels
     constexpr bool built = !PAIR;
 #else
     constexpr bool built = true;
 #endif
     if constexpr (!built) return nullptr;
-    else return jb_forward_kernel<PAIR>;
-}
-typedef void (*ContactsKernel)(KArgs, CtArgs);
-template <bool PAIR> static ContactsKernel contacts_kernel() {
-#ifdef JB_DEV_ONLY4
-    constexpr bool built = !PAIR;
-#else
-    constexpr bool built = true;
-#endif
-    if constexpr (!built) return nullptr;
+    else if constexpr (std::is_same<Args, FwArgs>::value) return jb_forward_kernel<PAIR>;
     else return jb_contacts_kernel<PAIR>;
 }
 static int kernel_variant(const KArgs& k) { return step_variant(k.lean, k.pair, k.per_env_model, k.epw); }
@@ -1156,11 +1126,38 @@ static int upload_model(jb_handle* h, const double* params, int n_tables) {
     install_model(h, std::move(fresh), per_env_model, pair);
     return JB_OK;
 }
-// grow-only device staging of any element type (ensure_stage below is the float form the rollouts use)
+// grow-only device staging owned by the handle, of any element type: (re)allocated only when a call needs more than any call before it
 template <typename T> static int grow_stage(jb_handle* h, Dev<T>& buf, size_t n, const char* what) {
     if (n <= buf.size()) return JB_OK;
     if (buf) JB_HIP(hipStreamSynchronize(h->stream));      // (the buffer may still be in use by queued work)
     if (buf.alloc(n) != hipSuccess) return fail(JB_E_HIP, std::string("out of device memory for ") + what);
+    return JB_OK;
+}
+
+// The host-buffer forms of the passes over states (jb_readout, jb_forward, jb_contacts) stage through one grow-only buffer of the handle, cut into the call's parts back to back in table order (every
+// part but a last one of bytes is whole 4-byte words, and the tables put the parts whose lengths are multiples of 16 bytes first).  A part
+// whose host pointer is NULL is absent: dev() is NULL and nothing is copied.
+struct StagePart {
+    void* host; size_t bytes; bool upload;
+    char* at;
+    template <typename T> T* dev() const { return host ? (T*)at : nullptr; }
+};
+template <size_t P> static int stage_parts(jb_handle* h, Dev<float>& buf, StagePart (&part)[P], const char* what) {
+    size_t total = 0;
+    for (const StagePart& q : part) total += q.bytes;
+    int rc = grow_stage(h, buf, (total + 3) / 4, what);
+    if (rc) return rc;
+    char* at = (char*)buf.get();
+    for (StagePart& q : part) {
+        q.at = at; at += q.bytes;
+        if (q.upload && q.host) JB_HIP(hipMemcpyAsync(q.at, q.host, q.bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    return JB_OK;
+}
+template <size_t P> static int fetch_parts(jb_handle* h, const StagePart (&part)[P]) {
+    for (const StagePart& q : part)
+        if (!q.upload && q.host) JB_HIP(hipMemcpyAsync(q.host, q.at, q.bytes, hipMemcpyDeviceToHost, h->stream));
+    JB_HIP(hipStreamSynchronize(h->stream));
     return JB_OK;
 }
 
@@ -1489,13 +1486,6 @@ int jb_step_many_device(jb_handle* h, int32_t n_steps, const float* d_actions, f
     io.every_step = 2;
     return launch_step(h, io, 0);
 }
-// grow-only device staging owned by the handle: (re)allocated only when a call needs more than any call before it
-static int ensure_stage(jb_handle* h, Dev<float>& buf, size_t floats, const char* what) {
-    if (floats <= buf.size()) return JB_OK;
-    if (buf) JB_HIP(hipStreamSynchronize(h->stream));      // (the buffer may still be in use by queued work)
-    if (buf.alloc(floats) != hipSuccess) return fail(JB_E_HIP, std::string("out of device memory for ") + what);
-    return JB_OK;
-}
 // host-buffer form of jb_step_many_device: actions [K, N] (NULL: the in-kernel heuristic policy), rows_out [K, N, D+2] (nullable);
 // the device staging belongs to the handle and only ever grows (no allocation after the first call of a given size); the results are valid on return
 int jb_step_many(jb_handle* h, int32_t n_steps, const float* actions, float* rows_out) {
@@ -1506,11 +1496,11 @@ int jb_step_many(jb_handle* h, int32_t n_steps, const float* actions, float* row
     const size_t N = (size_t)h->cfg.n_envs, K = (size_t)n_steps, W = (size_t)h->D + 2;
     int rc = JB_OK;
     if (actions) {
-        rc = ensure_stage(h, h->d_tape, K * N, "the action tape");
+        rc = grow_stage(h, h->d_tape, K * N, "the action tape");
         if (rc) return rc;
         JB_HIP(hipMemcpyAsync(h->d_tape.get(), actions, sizeof(float) * K * N, hipMemcpyHostToDevice, h->stream));
     }
-    if (rows_out) { rc = ensure_stage(h, h->d_rows_stage, K * N * W, "the rows"); if (rc) return rc; }
+    if (rows_out) { rc = grow_stage(h, h->d_rows_stage, K * N * W, "the rows"); if (rc) return rc; }
     rc = jb_step_many_device(h, n_steps, actions ? h->d_tape.get() : nullptr, rows_out ? h->d_rows_stage.get() : nullptr, nullptr, nullptr, nullptr);
     if (!rc && rows_out && hipMemcpyAsync(rows_out, h->d_rows_stage.get(), sizeof(float) * K * N * W, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "jb_step_many: copy of the rows failed");
     const hipError_t e = hipStreamSynchronize(h->stream);
@@ -1615,7 +1605,7 @@ int jb_score_tapes_device(jb_handle* h, int32_t n_steps, const float* d_tapes, f
     if (h->async_pending) return fail(JB_E_INVALID, "jb_score_tapes_device: a jb_step_async is pending (jb_step_wait first)");
     RoctxRange range("jb_score_tapes");
     const size_t N = (size_t)h->cfg.n_envs, K = (size_t)n_steps;
-    int rc = ensure_stage(h, h->d_rew_stage, K * N, "the rewards");
+    int rc = grow_stage(h, h->d_rew_stage, K * N, "the rewards");
     if (!rc) rc = grow_stage(h, h->d_done_stage, K * N, "the done flags");
     if (rc) return rc;
     StepIO io = StepIO();
@@ -1628,98 +1618,94 @@ int jb_score_tapes_device(jb_handle* h, int32_t n_steps, const float* d_tapes, f
     JB_HIP(hipGetLastError());
     return JB_OK;
 }
+// ---------------------------------------------------------------------------------------------- passes over states: readout, forward dynamics, contacts
+// What every pass refuses before it touches anything, under the name of the entry point `fn` (`n_out` spells how many outputs it has); then
+// `first` is snapshot 0 of the stack, or the handle's own blocks.
+static int check_pass(jb_handle* h, const std::string& fn, const void* d_snaps, int n_snaps, bool any_output, const char* n_out, SnapView* first = nullptr) {
+    if (n_snaps < 1) return fail(JB_E_INVALID, fn + ": n_snaps must be >= 1");
+    if (!any_output) return fail(JB_E_INVALID, fn + ": all " + n_out + " outputs are NULL");
+    if (h->async_pending) return fail(JB_E_INVALID, fn + ": a jb_step_async is pending (jb_step_wait first)");
+    if (!d_snaps && n_snaps != 1) return fail(JB_E_INVALID, fn + ": the handle's current state is ONE state (n_snaps must be 1 without a snapshot stack)");
+    if (first) *first = d_snaps ? snap_view(const_cast<void*>(d_snaps), h->cfg.n_envs) : state_view(h);      // (const_cast: the passes only read)
+    return JB_OK;
+}
+static int check_grid(const std::string& fn, long long blocks) {
+    return blocks > 0x7fffffffLL ? fail(JB_E_INVALID, fn + ": too many env-states for one launch") : JB_OK;
+}
+// The launch of a substep pass (PassWave): n_snaps x ceil(N / 4) waves of the step kernels' layout at four envs per wave, whichever kernel the handle steps with.
+struct PassLaunch {
+    KArgs a;
+    PassArgs p;
+    dim3 grid;
+    size_t lds_bytes;            // scratch and tables (step_lds_bytes)
+};
+static int prepare_pass(jb_handle* h, const std::string& fn, const void* d_snaps, int n_snaps, bool any_output, const char* n_out, const float* d_ctrl, uint8_t* d_unconverged, PassLaunch& l) {
+    int rc = check_pass(h, fn, d_snaps, n_snaps, any_output, n_out, &l.p.first);
+    if (rc) return rc;
+    const int N = h->cfg.n_envs;
+    l.a = h->ka;
+    l.a.epw = FW_EPW; l.a.lean = 0;
+    l.p.stride_words = (long long)SNAP_WORDS * N;
+    l.p.waves_per_snap = (N + FW_EPW - 1) / FW_EPW;
+    l.p.ctrl = d_ctrl; l.p.unconv = d_unconverged;
+    const long long blocks = (long long)n_snaps * l.p.waves_per_snap;
+    l.grid = dim3((unsigned)blocks);
+    l.lds_bytes = step_lds_bytes(step_layout(FW_EPW, false, h->ka.pair != 0), h->ka.per_env_model != 0);
+    return check_grid(fn, blocks);
+}
 // The readout pass (jb_readout.hpp): one launch over n_snaps * N env-states, a quad of lanes each; reads the state, writes only its outputs.
 int jb_readout_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, float* d_frames, float* d_clearance, float* d_body_vel, float* d_energy) {
     JB_ENTER(h);
-    if (n_snaps < 1) return fail(JB_E_INVALID, "jb_readout_device: n_snaps must be >= 1");
-    if (!d_frames && !d_clearance && !d_body_vel && !d_energy) return fail(JB_E_INVALID, "jb_readout_device: all four outputs are NULL");
-    if (h->async_pending) return fail(JB_E_INVALID, "jb_readout_device: a jb_step_async is pending (jb_step_wait first)");
-    if (!d_snaps && n_snaps != 1) return fail(JB_E_INVALID, "jb_readout_device: the handle's current state is ONE state (n_snaps must be 1 without a snapshot stack)");
+    RoArgs a;
+    int rc = check_pass(h, "jb_readout_device", d_snaps, n_snaps, d_frames || d_clearance || d_body_vel || d_energy, "four", &a.first);
+    if (rc) return rc;
     RoctxRange range("jb_readout");
     const int N = h->cfg.n_envs;
-    RoArgs a;
-    a.first = d_snaps ? snap_view(const_cast<void*>(d_snaps), N) : state_view(h);      // (const_cast: the pass only reads)
     a.stride_words = (long long)SNAP_WORDS * N;
     a.total = (long long)n_snaps * N;
     a.tab = h->ka.lane_model; a.n_tab = h->ka.per_env_model ? N : 1;
     a.frames = d_frames; a.clear = d_clearance; a.bvel = d_body_vel; a.energy = d_energy;
     a.vec4 = ((((uintptr_t)d_frames | (uintptr_t)d_clearance | (uintptr_t)d_body_vel | (uintptr_t)d_energy) & 15u) == 0) ? 1 : 0;
     const long long blocks = (a.total + RO_EPB - 1) / RO_EPB;
-    if (blocks > 0x7fffffffLL) return fail(JB_E_INVALID, "jb_readout_device: too many env-states for one launch");
+    rc = check_grid("jb_readout_device", blocks);
+    if (rc) return rc;
     hipLaunchKernelGGL(jb_readout_kernel, dim3((unsigned)blocks), dim3(64), 0, h->stream, a);
     JB_HIP(hipGetLastError());
     return JB_OK;
 }
 int jb_readout(jb_handle* h, float* frames, float* clearance, float* body_vel, float* energy) {
     JB_ENTER(h);
-    if (!frames && !clearance && !body_vel && !energy) return fail(JB_E_INVALID, "jb_readout: all four outputs are NULL");
-    if (h->async_pending) return fail(JB_E_INVALID, "jb_readout: a jb_step_async is pending (jb_step_wait first)");
-    const size_t N = (size_t)h->cfg.n_envs;
-    int rc = grow_stage(h, h->d_readout_stage, N * (size_t)(RO_FRAMES + RO_CLEAR + RO_BVEL + RO_ENERGY), "the readout");
-    if (rc) return rc;
-    // (laid out [frames | body_vel | energy | clearance]: the first three lengths are multiples of four floats, so every part starts on a 16-byte word)
-    float* d_fr = h->d_readout_stage.get();
-    float* d_bv = d_fr + N * RO_FRAMES;
-    float* d_en = d_bv + N * RO_BVEL;
-    float* d_cl = d_en + N * RO_ENERGY;
-    rc = jb_readout_device(h, nullptr, 1, frames ? d_fr : nullptr, clearance ? d_cl : nullptr, body_vel ? d_bv : nullptr, energy ? d_en : nullptr);
-    if (rc) return rc;
-    if (frames) JB_HIP(hipMemcpyAsync(frames, d_fr, sizeof(float) * N * RO_FRAMES, hipMemcpyDeviceToHost, h->stream));
-    if (clearance) JB_HIP(hipMemcpyAsync(clearance, d_cl, sizeof(float) * N * RO_CLEAR, hipMemcpyDeviceToHost, h->stream));
-    if (body_vel) JB_HIP(hipMemcpyAsync(body_vel, d_bv, sizeof(float) * N * RO_BVEL, hipMemcpyDeviceToHost, h->stream));
-    if (energy) JB_HIP(hipMemcpyAsync(energy, d_en, sizeof(float) * N * RO_ENERGY, hipMemcpyDeviceToHost, h->stream));
-    JB_HIP(hipStreamSynchronize(h->stream));
-    return JB_OK;
+    const size_t F = sizeof(float) * (size_t)h->cfg.n_envs;
+    StagePart part[] = {{frames, F * RO_FRAMES}, {body_vel, F * RO_BVEL}, {energy, F * RO_ENERGY}, {clearance, F * RO_CLEAR}};
+    int rc = check_pass(h, "jb_readout", nullptr, 1, frames || clearance || body_vel || energy, "four");
+    if (!rc) rc = stage_parts(h, h->d_readout_stage, part, "the readout");
+    if (!rc) rc = jb_readout_device(h, nullptr, 1, part[0].dev<float>(), part[3].dev<float>(), part[1].dev<float>(), part[2].dev<float>());
+    return rc ? rc : fetch_parts(h, part);
 }
-// The forward-dynamics pass (jb_forward_kernel above): one launch over n_snaps * ceil(N / 4) waves; reads the state, writes only its outputs.
+// The forward-dynamics pass (jb_forward_kernel above): reads the state, writes only its outputs.
 int jb_forward_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, const float* d_ctrl, float* d_qacc, float* d_qfrc, float* d_body_acc, float* d_motor, uint8_t* d_unconverged) {
     JB_ENTER(h);
-    if (n_snaps < 1) return fail(JB_E_INVALID, "jb_forward_device: n_snaps must be >= 1");
-    if (!d_qacc && !d_qfrc && !d_body_acc && !d_motor && !d_unconverged) return fail(JB_E_INVALID, "jb_forward_device: all five outputs are NULL");
-    if (h->async_pending) return fail(JB_E_INVALID, "jb_forward_device: a jb_step_async is pending (jb_step_wait first)");
-    if (!d_snaps && n_snaps != 1) return fail(JB_E_INVALID, "jb_forward_device: the handle's current state is ONE state (n_snaps must be 1 without a snapshot stack)");
-    const ForwardKernel kernel = h->ka.pair ? forward_kernel<true>() : forward_kernel<false>();
+    PassLaunch l;
+    int rc = prepare_pass(h, "jb_forward_device", d_snaps, n_snaps, d_qacc || d_qfrc || d_body_acc || d_motor || d_unconverged, "five", d_ctrl, d_unconverged, l);
+    if (rc) return rc;
+    const PassKernel<FwArgs> kernel = h->ka.pair ? pass_kernel<FwArgs, true>() : pass_kernel<FwArgs, false>();
     if (!kernel) return fail(JB_E_INVALID, "JB_DEV_ONLY4 build: only the forward pass without the pair contacts");
     RoctxRange range("jb_forward");
-    const int N = h->cfg.n_envs;
-    const StepLayout lay = step_layout(FW_EPW, false, h->ka.pair != 0);
-    KArgs a = h->ka;
-    a.epw = FW_EPW; a.lean = 0;      // the pass has its own layout, whichever kernel the handle steps with
     FwArgs f;
-    f.first = d_snaps ? snap_view(const_cast<void*>(d_snaps), N) : state_view(h);      // (const_cast: the pass only reads)
-    f.stride_words = (long long)SNAP_WORDS * N;
-    f.waves_per_snap = (N + FW_EPW - 1) / FW_EPW;
-    f.ctrl = d_ctrl;
-    f.qacc = d_qacc; f.qfrc = d_qfrc; f.bacc = d_body_acc; f.motor = d_motor; f.unconv = d_unconverged;
-    const long long blocks = (long long)n_snaps * f.waves_per_snap;
-    if (blocks > 0x7fffffffLL) return fail(JB_E_INVALID, "jb_forward_device: too many env-states for one launch");
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), step_lds_bytes(lay, h->ka.per_env_model != 0), h->stream, a, f);
+    f.p = l.p;
+    f.qacc = d_qacc; f.qfrc = d_qfrc; f.bacc = d_body_acc; f.motor = d_motor;
+    hipLaunchKernelGGL(kernel, l.grid, dim3(64), l.lds_bytes, h->stream, l.a, f);
     JB_HIP(hipGetLastError());
     return JB_OK;
 }
 int jb_forward(jb_handle* h, const float* ctrl, float* qacc, float* qfrc, float* body_acc, float* motor, uint8_t* unconverged) {
     JB_ENTER(h);
-    if (!qacc && !qfrc && !body_acc && !motor && !unconverged) return fail(JB_E_INVALID, "jb_forward: all five outputs are NULL");
-    if (h->async_pending) return fail(JB_E_INVALID, "jb_forward: a jb_step_async is pending (jb_step_wait first)");
-    const size_t N = (size_t)h->cfg.n_envs;
-    int rc = grow_stage(h, h->d_forward_stage, N * (size_t)(FW_BACC + 2 * FW_NV + FW_MOTOR + 1) + (N + 3) / 4, "the forward pass");
-    if (rc) return rc;
-    float* d_ba = h->d_forward_stage.get();
-    float* d_qa = d_ba + N * FW_BACC;
-    float* d_qf = d_qa + N * FW_NV;
-    float* d_mo = d_qf + N * FW_NV;
-    float* d_u = d_mo + N * FW_MOTOR;
-    uint8_t* d_un = (uint8_t*)(d_u + N);
-    if (ctrl) JB_HIP(hipMemcpyAsync(d_u, ctrl, sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
-    rc = jb_forward_device(h, nullptr, 1, ctrl ? d_u : nullptr, qacc ? d_qa : nullptr, qfrc ? d_qf : nullptr, body_acc ? d_ba : nullptr, motor ? d_mo : nullptr, unconverged ? d_un : nullptr);
-    if (rc) return rc;
-    if (qacc) JB_HIP(hipMemcpyAsync(qacc, d_qa, sizeof(float) * N * FW_NV, hipMemcpyDeviceToHost, h->stream));
-    if (qfrc) JB_HIP(hipMemcpyAsync(qfrc, d_qf, sizeof(float) * N * FW_NV, hipMemcpyDeviceToHost, h->stream));
-    if (body_acc) JB_HIP(hipMemcpyAsync(body_acc, d_ba, sizeof(float) * N * FW_BACC, hipMemcpyDeviceToHost, h->stream));
-    if (motor) JB_HIP(hipMemcpyAsync(motor, d_mo, sizeof(float) * N * FW_MOTOR, hipMemcpyDeviceToHost, h->stream));
-    if (unconverged) JB_HIP(hipMemcpyAsync(unconverged, d_un, N, hipMemcpyDeviceToHost, h->stream));
-    JB_HIP(hipStreamSynchronize(h->stream));
-    return JB_OK;
+    const size_t N = (size_t)h->cfg.n_envs, F = sizeof(float) * N;
+    StagePart part[] = {{body_acc, F * FW_BACC}, {qacc, F * FW_NV}, {qfrc, F * FW_NV}, {motor, F * FW_MOTOR}, {const_cast<float*>(ctrl), F, true}, {unconverged, N}};
+    int rc = check_pass(h, "jb_forward", nullptr, 1, qacc || qfrc || body_acc || motor || unconverged, "five");
+    if (!rc) rc = stage_parts(h, h->d_forward_stage, part, "the forward pass");
+    if (!rc) rc = jb_forward_device(h, nullptr, 1, part[4].dev<float>(), part[1].dev<float>(), part[2].dev<float>(), part[0].dev<float>(), part[3].dev<float>(), part[5].dev<uint8_t>());
+    return rc ? rc : fetch_parts(h, part);
 }
 // The contact pass (jb_contacts_kernel above): the forward pass's launch with the output images behind the scratch and the tables in LDS.
 static_assert(JB_NCONTACT == CT_NROW && JB_CONTACT_WIDTH == CT_W, "the header states the table's shape");
@@ -1729,53 +1715,28 @@ int32_t jb_contact_rows(void) { return CT_NROW; }
 void jb_contact_slot_geoms(int32_t* out) { if (out) ct_slot_geoms(out); }
 int jb_contacts_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, const float* d_ctrl, float* d_contact, int32_t* d_ncon, float* d_geom_frc, uint8_t* d_unconverged) {
     JB_ENTER(h);
-    if (n_snaps < 1) return fail(JB_E_INVALID, "jb_contacts_device: n_snaps must be >= 1");
-    if (!d_contact && !d_ncon && !d_geom_frc && !d_unconverged) return fail(JB_E_INVALID, "jb_contacts_device: all four outputs are NULL");
-    if (h->async_pending) return fail(JB_E_INVALID, "jb_contacts_device: a jb_step_async is pending (jb_step_wait first)");
-    if (!d_snaps && n_snaps != 1) return fail(JB_E_INVALID, "jb_contacts_device: the handle's current state is ONE state (n_snaps must be 1 without a snapshot stack)");
-    const ContactsKernel kernel = h->ka.pair ? contacts_kernel<true>() : contacts_kernel<false>();
+    PassLaunch l;
+    int rc = prepare_pass(h, "jb_contacts_device", d_snaps, n_snaps, d_contact || d_ncon || d_geom_frc || d_unconverged, "four", d_ctrl, d_unconverged, l);
+    if (rc) return rc;
+    const PassKernel<CtArgs> kernel = h->ka.pair ? pass_kernel<CtArgs, true>() : pass_kernel<CtArgs, false>();
     if (!kernel) return fail(JB_E_INVALID, "JB_DEV_ONLY4 build: only the contact pass without the pair contacts");
     RoctxRange range("jb_contacts");
-    const int N = h->cfg.n_envs;
-    const StepLayout lay = step_layout(FW_EPW, false, h->ka.pair != 0);
-    KArgs a = h->ka;
-    a.epw = FW_EPW; a.lean = 0;      // the pass has its own layout, whichever kernel the handle steps with
     CtArgs f;
-    f.first = d_snaps ? snap_view(const_cast<void*>(d_snaps), N) : state_view(h);      // (const_cast: the pass only reads)
-    f.stride_words = (long long)SNAP_WORDS * N;
-    f.waves_per_snap = (N + FW_EPW - 1) / FW_EPW;
-    const size_t step_bytes = step_lds_bytes(lay, h->ka.per_env_model != 0);
-    f.img = (int)((step_bytes + 15) / 16 * 4);
-    f.ctrl = d_ctrl;
-    f.contact = d_contact; f.geom_frc = d_geom_frc; f.ncon = d_ncon; f.unconv = d_unconverged;
-    const long long blocks = (long long)n_snaps * f.waves_per_snap;
-    if (blocks > 0x7fffffffLL) return fail(JB_E_INVALID, "jb_contacts_device: too many env-states for one launch");
-    const size_t lds_bytes = ((size_t)f.img + CT_LDS_FLOATS) * sizeof(float);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), lds_bytes, h->stream, a, f);
+    f.p = l.p;
+    f.img = (int)((l.lds_bytes + 15) / 16 * 4);
+    f.contact = d_contact; f.geom_frc = d_geom_frc; f.ncon = d_ncon;
+    hipLaunchKernelGGL(kernel, l.grid, dim3(64), ((size_t)f.img + CT_LDS_FLOATS) * sizeof(float), h->stream, l.a, f);
     JB_HIP(hipGetLastError());
     return JB_OK;
 }
 int jb_contacts(jb_handle* h, const float* ctrl, float* contact, int32_t* ncon, float* geom_frc, uint8_t* unconverged) {
     JB_ENTER(h);
-    if (!contact && !ncon && !geom_frc && !unconverged) return fail(JB_E_INVALID, "jb_contacts: all four outputs are NULL");
-    if (h->async_pending) return fail(JB_E_INVALID, "jb_contacts: a jb_step_async is pending (jb_step_wait first)");
-    const size_t N = (size_t)h->cfg.n_envs;
-    int rc = grow_stage(h, h->d_contacts_stage, N * (size_t)(CT_TABLE + CT_GEOMF + 2) + (N + 3) / 4, "the contact pass");
-    if (rc) return rc;
-    float* d_ct = h->d_contacts_stage.get();
-    float* d_gf = d_ct + N * CT_TABLE;
-    float* d_u = d_gf + N * CT_GEOMF;
-    int32_t* d_nc = (int32_t*)(d_u + N);
-    uint8_t* d_un = (uint8_t*)(d_nc + N);
-    if (ctrl) JB_HIP(hipMemcpyAsync(d_u, ctrl, sizeof(float) * N, hipMemcpyHostToDevice, h->stream));
-    rc = jb_contacts_device(h, nullptr, 1, ctrl ? d_u : nullptr, contact ? d_ct : nullptr, ncon ? d_nc : nullptr, geom_frc ? d_gf : nullptr, unconverged ? d_un : nullptr);
-    if (rc) return rc;
-    if (contact) JB_HIP(hipMemcpyAsync(contact, d_ct, sizeof(float) * N * CT_TABLE, hipMemcpyDeviceToHost, h->stream));
-    if (ncon) JB_HIP(hipMemcpyAsync(ncon, d_nc, sizeof(int32_t) * N, hipMemcpyDeviceToHost, h->stream));
-    if (geom_frc) JB_HIP(hipMemcpyAsync(geom_frc, d_gf, sizeof(float) * N * CT_GEOMF, hipMemcpyDeviceToHost, h->stream));
-    if (unconverged) JB_HIP(hipMemcpyAsync(unconverged, d_un, N, hipMemcpyDeviceToHost, h->stream));
-    JB_HIP(hipStreamSynchronize(h->stream));
-    return JB_OK;
+    const size_t N = (size_t)h->cfg.n_envs, F = sizeof(float) * N;
+    StagePart part[] = {{contact, F * CT_TABLE}, {geom_frc, F * CT_GEOMF}, {const_cast<float*>(ctrl), F, true}, {ncon, sizeof(int32_t) * N}, {unconverged, N}};
+    int rc = check_pass(h, "jb_contacts", nullptr, 1, contact || ncon || geom_frc || unconverged, "four");
+    if (!rc) rc = stage_parts(h, h->d_contacts_stage, part, "the contact pass");
+    if (!rc) rc = jb_contacts_device(h, nullptr, 1, part[2].dev<float>(), part[0].dev<float>(), part[3].dev<int32_t>(), part[1].dev<float>(), part[4].dev<uint8_t>());
+    return rc ? rc : fetch_parts(h, part);
 }
 // how long each wave of the last step launch lived, in seconds (s_memrealtime, 100 MHz): out[0 .. n_waves); returns the number of waves
 int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves) {
@@ -1906,7 +1867,7 @@ int jb_rollout_policy(jb_handle* h, int32_t n_steps, float* rewards_out /*[K,N] 
     JB_ENTER(h);
     const size_t N = (size_t)h->cfg.n_envs;
     const bool want_rew = rewards_out && n_steps > 0;
-    if (want_rew) { int rc0 = ensure_stage(h, h->d_rew_stage, N * (size_t)n_steps, "the rewards"); if (rc0) return rc0; }
+    if (want_rew) { int rc0 = grow_stage(h, h->d_rew_stage, N * (size_t)n_steps, "the rewards"); if (rc0) return rc0; }
     int rc = jb_observe_device(h, h->d_obs.get(), nullptr);
     if (!rc) rc = jb_rollout_policy_device(h, n_steps, h->d_obs.get(), want_rew ? h->d_rew_stage.get() : nullptr, nullptr);
     if (!rc && want_rew && hipMemcpyAsync(rewards_out, h->d_rew_stage.get(), sizeof(float) * N * (size_t)n_steps, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(JB_E_HIP, "copy of rewards failed");

@@ -1,5 +1,5 @@
 // contacts_harness.cpp — the contact pass compiled for the host (test infrastructure): ONE substep of jb_sim.hpp on the lane layout of the
-// step kernels (tests/host_harness.cpp HostRun; tests/forward_harness.cpp's state loading, included as they are) with a SolveTap, then the
+// step kernels (tests/pass_harness.hpp one_substep) with a SolveTap, then the
 // per-slot function of jitterbug_amd/csrc/jb_contacts.hpp on the scratch the substep left, slot by slot as jb_contacts_kernel walks them,
 // and - for the tests' sum checks - jb_forward.hpp's qfrc from the same y.
 //
@@ -7,42 +7,33 @@
 //   g++ -shared                                   jbc_run_f32 / jbc_run_f64 below, driven from numpy through ctypes
 //   g++ -DJBC_MAIN -fsanitize=address,undefined   a stand-alone program: ragged sizes, absent outputs and a stack on heap blocks of exactly
 //                                                 the promised sizes (main lanes only: no threads under the sanitizer)
-#include "forward_harness.cpp"
+#define JB_PASS_SUBSTEP
+#include "pass_harness.hpp"
 
 #include "../jitterbug_amd/csrc/jb_contacts.hpp"
 
-// as forward() of forward_harness.cpp; contact [n_snaps * N, CT_NROW, CT_W], ncon [n_snaps * N], gfrc [n_snaps * N, 22, 3], qfrc [n_snaps * N, 15]
+// arguments as forward() of forward_harness.cpp; contact [n_snaps * N, CT_NROW, CT_W], ncon [n_snaps * N], gfrc [n_snaps * N, 22, 3], qfrc [n_snaps * N, 15]
 // (the forward pass's, from the same substep), unconv: each nullable
 template <typename T> static int contacts(const uint32_t* snaps, int N, int n_snaps, const double* P, int n_models, const double* ctrl, int ngroups, int pair,
                                           T* contact, int32_t* ncon, T* gfrc, T* qfrc, unsigned char* unconv) {
     using V = Quad<T>;
-    if (ngroups != 1 && ngroups != 4) return -101;
-    std::vector<HostRun<T>> runs(n_models);
-    for (int t = 0; t < n_models; t++)
-        if (int rc = runs[t].init(P + (size_t)t * JB_NPARAM, ngroups, false, pair != 0, 1, 12, 1, 1)) return rc;
+    std::vector<HostRun<T>> runs;
+    if (int rc = pass_runs<T>(P, n_models, ngroups, pair, runs)) return rc;
     for (long long es = 0; es < (long long)n_snaps * N; es++) {
         const long long k = es / N, env = es - k * N;
         const SnapView v = snap_view(const_cast<uint32_t*>(snaps) + (size_t)k * SNAP_WORDS * N, N);
         HostRun<T>& w = runs[env % n_models];
         const T u = ctrl ? T(ctrl[es]) : T(0);
-        LaneState<V> s = state_from_words<T>(v, env), s1;
-        normalise_state(s);
-        CtTap<V> tap0;
-        LaneScratch<V> sc0;
-        w.run(s, [&](typename HostRun<T>::Group& G) {
-            w.before_substep(G, true, true);          // the pair narrow phase starts cold: the first substep of a control step
-            CtTap<V> mine;
-            if (pair) substep<V, true, SolveTap<V>>(*G.m, G.sc, G.s, V(u), w.o, mine.tap()); else substep<V, false, SolveTap<V>>(*G.m, G.sc, G.s, V(u), w.o, mine.tap());
-            if (G.g == 0) { s1 = G.s; tap0 = mine; sc0 = G.sc; }
-        });
+        const auto sub = one_substep<T, CtTap<V>>(pair, w, v, env, u);
+        const LaneScratch<V>& sc0 = sub.sc;
         // the pose, as the kernel takes it: the readout's loads of the untouched input state
         const RoState<T> st = ro_load<T>(v, env, 0);
         const Mat3<T> R = ro_quat2mat(st.q, st.ql);
         CtPose<V> pose;
         for (int i = 0; i < 9; i++) pose.R.m[i] = V(R.m[i]);
         pose.px = V(st.px); pose.py = V(st.py); pose.pz = V(st.pz); pose.pz_lo = V(st.pz_lo);
-        const unsigned live = tap0.live;
-        const CtY<V> y = ct_y<V>(sc0, tap0);
+        const unsigned live = sub.tap.live;
+        const CtY<V> y = ct_y<V>(sc0, sub.tap);
         T* rows = contact ? contact + (size_t)es * CT_TABLE : nullptr;
         T* gf = gfrc ? gfrc + (size_t)es * CT_GEOMF : nullptr;
         if (rows) for (int i = 0; i < CT_TABLE; i++) rows[i] = T(0);
@@ -63,16 +54,9 @@ template <typename T> static int contacts(const uint32_t* snaps, int N, int n_sn
         if (qfrc) {
             FwOut<T> o;
             o.qacc = nullptr; o.qfrc = qfrc + (size_t)es * FW_NV; o.bacc = nullptr; o.motor = nullptr;
-            T p[4][6];
-            for (int leg = 0; leg < 4; leg++) {
-                FwAcc<T> a;
-                for (int i = 0; i < 3; i++) { a.lin[i] = s1.wl[i].v[leg]; a.ang[i] = s1.wa[i].v[leg]; }
-                a.j1 = s1.wj[0].v[leg]; a.j2 = s1.wj[1].v[leg]; a.m = s1.wm.v[leg];
-                fw_lane<T>(fw_load<T>(v, env, leg), a, u, w.tab, leg, o, p[leg]);
-            }
-            for (int i = 0; i < 6; i++) o.qfrc[i] = ro_quad_total(p[0][i], p[1][i], p[2][i], p[3][i]);
+            fw_qfrc<T>(v, env, sub.s, u, w.tab, o);
         }
-        if (unconv) unconv[es] = s1.fail.v[0] > T(0) ? 1 : 0;
+        if (unconv) unconv[es] = sub.s.fail.v[0] > T(0) ? 1 : 0;
     }
     return 0;
 }
@@ -92,31 +76,10 @@ void jbc_slot_geoms(int32_t* out) { ct_slot_geoms(out); }
 #ifdef JBC_MAIN
 #include "../jitterbug_amd/csrc/jb_default_params.h"
 
-// states on or below the floor, every one different: the robot lowered so that feet and legs touch, tilted further with the env index
-static std::vector<uint32_t> synth_low(int N, int n_snaps) {
-    std::vector<uint32_t> s((size_t)SNAP_WORDS * N * n_snaps, 0u);
-    auto put = [](uint32_t* p, float x) { std::memcpy(p, &x, 4); };
-    for (int k = 0; k < n_snaps; k++) {
-        SnapView v = snap_view(s.data() + (size_t)k * SNAP_WORDS * N, N);
-        for (int e = 0; e < N; e++) {
-            const float a = 0.08f * (float)(e % 9) + 0.03f * (float)k;
-            const double q[4] = {std::cos(0.5 * a), 0.6 * std::sin(0.5 * a), 0.8 * std::sin(0.5 * a), 0.0};
-            float r[SNAP_ROOT_F] = {0};
-            r[RO_RF_P] = 0.1f * (float)e; r[RO_RF_P + 1] = -0.05f * (float)k; r[RO_RF_P + 2] = 0.012f + 0.002f * (float)((e + k) % 4);
-            for (int i = 0; i < 4; i++) { r[RO_RF_Q + i] = (float)q[i]; r[RO_RF_LO + 1 + i] = (float)(q[i] - (double)(float)q[i]); }
-            for (int i = 0; i < 6; i++) r[RO_RF_V + i] = 0.01f * (float)(i + 1) * (float)(e % 5 + 1);
-            r[RO_RF_PHI] = 0.5f * (float)(e % 6) - 1.f; r[RO_RF_PHID] = 30.f;
-            for (int f = 0; f < SNAP_ROOT_F; f++) put(&v.root[(size_t)f * N + e], r[f]);
-            for (int l = 0; l < 4; l++) {
-                const float lf[SNAP_LEG_F] = {0.05f * (float)(l + 1), -0.04f * (float)(l + 1) + 0.01f * (float)k, 0.3f, -0.2f, 0.f, 0.f};
-                for (int f = 0; f < SNAP_LEG_F; f++) put(&v.leg[(size_t)f * 4 * N + 4 * e + l], lf[f]);
-            }
-        }
-    }
-    return s;
-}
+// on or below the floor: the robot lowered so that feet and legs touch, tilted further with the env index
+static const SynthSpec STATES = {0.08f, 0.03f, 9, 2, 0.012f, 0.002f, 0.f, 5, 6, 30.f, false, -1, 0.05f, -0.04f};
 static int check_case(int N, int n_snaps, int pair) {
-    const std::vector<uint32_t> s = synth_low(N, n_snaps);
+    const std::vector<uint32_t> s = synth(STATES, N, n_snaps);
     const size_t M = (size_t)N * n_snaps;
     std::vector<double> u(M);
     for (size_t i = 0; i < M; i++) u[i] = 0.3 * (double)(i % 7) - 1.0;
@@ -132,23 +95,11 @@ static int check_case(int N, int n_snaps, int pair) {
         bad += act != nc[e];
         total += act;
     }
-    // absent outputs leave the present ones unchanged
-    for (int mask = 1; mask < 7; mask++) {
-        std::vector<float> ct2(M * CT_TABLE), gf2(M * CT_GEOMF);
-        std::vector<int32_t> nc2(M);
-        bad += jbc_run_f32(s.data(), N, n_snaps, JB_DEFAULT_PARAMS, 1, u.data(), 1, pair, (mask & 1) ? ct2.data() : nullptr, (mask & 2) ? nc2.data() : nullptr,
-                           (mask & 4) ? gf2.data() : nullptr, nullptr, nullptr) != 0;
-        if (mask & 1) bad += std::memcmp(ct.data(), ct2.data(), 4 * ct.size()) != 0;
-        if (mask & 2) bad += std::memcmp(nc.data(), nc2.data(), 4 * nc.size()) != 0;
-        if (mask & 4) bad += std::memcmp(gf.data(), gf2.data(), 4 * gf.size()) != 0;
-    }
-    // a stack in one call equals its snapshots one by one
-    for (int k = 0; k < n_snaps; k++) {
-        std::vector<uint32_t> one(s.begin() + (size_t)k * SNAP_WORDS * N, s.begin() + (size_t)(k + 1) * SNAP_WORDS * N);
-        std::vector<float> ct1((size_t)N * CT_TABLE);
-        bad += jbc_run_f32(one.data(), N, 1, JB_DEFAULT_PARAMS, 1, u.data() + (size_t)k * N, 1, pair, ct1.data(), nullptr, nullptr, nullptr, nullptr) != 0;
-        bad += std::memcmp(ct1.data(), ct.data() + (size_t)k * N * CT_TABLE, 4 * ct1.size()) != 0;
-    }
+    const void* const full[3] = {ct.data(), nc.data(), gf.data()};
+    const size_t es_bytes[3] = {4 * CT_TABLE, 4, 4 * CT_GEOMF};
+    bad += absent_and_stack_mismatches(s, N, n_snaps, full, es_bytes, 1u, [&](const uint32_t* snaps, int ns, size_t es0, void* const* o) {
+        return jbc_run_f32(snaps, N, ns, JB_DEFAULT_PARAMS, 1, u.data() + es0, 1, pair, (float*)o[0], (int32_t*)o[1], (float*)o[2], nullptr, nullptr);
+    });
     std::printf("N %3d  n_snaps %d  pair %d  %lld contacts: %s\n", N, n_snaps, pair, total, bad ? "MISMATCH" : "ok");
     return bad + (total == 0);
 }

@@ -1,7 +1,8 @@
-"""tools/asm_listing.py and the four reports over it (asm_spills / asm_copies / asm_exec_regions / asm_dpp_forms) plus kernel_resources.py, on a
+"""tools/asm_listing.py and the four reports over it (asm_spills / asm_copies / asm_exec_regions / asm_dpp_forms) plus kernel_resources.py and compare_listings.py, on a
 listing written by hand: no compiler, no GPU.  Every expected figure below is counted by hand from LISTING (the number in front of a line is its
 index within its function), not taken from a run of the tools."""
 import os
+import subprocess
 import sys
 
 import pytest
@@ -16,6 +17,7 @@ import asm_dpp_forms  # noqa: E402
 import asm_exec_regions  # noqa: E402
 import asm_listing  # noqa: E402
 import asm_spills  # noqa: E402
+import compare_listings  # noqa: E402
 import kernel_resources  # noqa: E402
 
 # A kernel that is not wanted (with a loop of its own), then a step kernel: the step loop's header .LBB1_1 takes TWO back-branches (43: the
@@ -195,3 +197,34 @@ def test_listing_command_follows_the_product_flags():
     assert "-DJB_DEV_ONLY4" in more and "-gline-tables-only" in more and [f for f in more if f in shipped] == shipped
     res = asm_listing.compile_command(["-c"], "/tmp/out.o", ["-Rpass-analysis=kernel-resource-usage"])
     assert "-c" in res and "-S" not in res and "--cuda-device-only" in res and [f for f in res if f in shipped] == shipped
+
+
+KERNEL = "_ZN12_GLOBAL__N_114jb_step_kernelILi4EEEvNS_5KArgsE:\n%s\ts_endpgm\n.Lfunc_end0:\n"
+BASE = ["s_and_b64 vcc, s[8:9], s[4:5]", "v_fma_f32 v1, -v2, v3, v4", "v_pk_fma_f32 v[0:1], v[2:3], v[4:5], v[6:7] op_sel_hi:[1,0,1]", "v_sub_f32_e32 v1, v2, v3",
+        "v_add_f32_dpp v5, v4, v6 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf", "v_mul_f32_e32 v1, v2, v3"]
+
+
+@pytest.mark.parametrize("at, line, commuted", [
+    (0, "s_and_b64 vcc, s[4:5], s[8:9]", True),                                              # a swapped scalar and
+    (1, "v_fma_f32 v1, v3, -v2, v4", True),                                                  # swapped multiplicands, the sign with its operand
+    (1, "v_fma_f32 v1, -v3, v2, v4", False),                                                 # ... the sign left behind
+    (1, "v_fma_f32 v1, -v2, v4, v3", False),                                                 # a swapped addend
+    (2, "v_pk_fma_f32 v[0:1], v[4:5], v[2:3], v[6:7] op_sel_hi:[0,1,1]", True),             # the per-source array entries move too
+    (2, "v_pk_fma_f32 v[0:1], v[4:5], v[2:3], v[6:7] op_sel_hi:[1,0,1]", False),
+    (3, "v_sub_f32_e32 v1, v3, v2", False),                                                  # an opcode outside the list
+    (4, "v_add_f32_dpp v5, v6, v4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf", False),   # DPP shuffles its first source only
+    (5, "v_mul_f32_e32 v2, v3, v1", False),                                                  # another destination
+    (5, "v_mul_f32_e64 v1, v3, v2", False),                                                  # another encoding is another opcode
+])
+def test_compare_listings_allow_commuted(tmp_path, at, line, commuted):
+    new = list(BASE)
+    new[at] = line
+    a, b = ["\t" + l for l in BASE], ["\t" + l for l in new]
+    assert compare_listings.compare(a, a, True) == [] and compare_listings.compare(a, b) is None and compare_listings.compare(a, b[:-1], True) is None
+    assert compare_listings.compare(a, b, True) == ([(at, a[at], b[at])] if commuted else None)
+    (tmp_path / "a.s").write_text(KERNEL % "".join(l + "\n" for l in a))
+    (tmp_path / "b.s").write_text(KERNEL % "".join(l + "\n" for l in b))
+    run = lambda *opt: subprocess.run([sys.executable, os.path.join(TOOLS, "compare_listings.py"), str(tmp_path / "a.s"), str(tmp_path / "b.s")] + list(opt), stdout=subprocess.PIPE, text=True)
+    plain, allowed = run(), run("--allow-commuted")
+    assert plain.returncode == 1 and plain.stdout.startswith("DIFFERS jb_step_kernel")
+    assert allowed.returncode == (0 if commuted else 1) and allowed.stdout.startswith("COMMUTED 1 jb_step_kernel" if commuted else "DIFFERS jb_step_kernel")

@@ -14,27 +14,17 @@ import numpy as np
 import pytest
 
 from jitterbug_amd import model
+from tests.build_harness import build_source
 from tests import forward_inputs as fi
 from tests import readout_inputs as ri
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "forward_harness.cpp")
-CSRC = os.path.join(HERE, "..", "jitterbug_amd", "csrc")
-DEPS = [SRC, os.path.join(HERE, "host_harness.cpp")] + [os.path.join(CSRC, f) for f in (
-    "jb_forward.hpp", "jb_readout.hpp", "jb_snapshot.hpp", "jb_sim.hpp", "jb_lane.hpp", "jb_step.hpp", "jb_task.hpp", "jb_variant.hpp", "jb_model_build.hpp", "jb_default_params.h")]
-
-
-def _build(out_name, extra):
-    out = os.path.join(HERE, "_build", out_name)
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not (os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in DEPS)):
-        subprocess.check_call(["g++", "-std=c++17", "-Wno-unknown-pragmas", "-pthread"] + extra + ["-o", out, SRC])
-    return out
 
 
 @pytest.fixture(scope="module")
 def hf():
-    lib = C.CDLL(_build("libjb_forward_host.so", ["-O2", "-fPIC", "-shared"]))
+    lib = C.CDLL(build_source(SRC, "libjb_forward_host.so", ["-pthread", "-O2", "-fPIC", "-shared"]))
     vp = C.c_void_p
     lib.jbf_run_f32.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.jbf_run_f64.argtypes = lib.jbf_run_f32.argtypes
@@ -167,7 +157,7 @@ def test_host_code_under_address_and_undefined_sanitizers():
     """The one sanitizer run of this code: a stand-alone program (its own main, tests/forward_harness.cpp -DJBF_MAIN) over ragged sizes,
     absent outputs and a 3-snapshot stack, with and without the PAIR substep, on heap blocks of exactly the promised sizes."""
     # (the sanitizer runtimes are linked statically: the program is complete in itself, whatever else the process environment loads)
-    exe = _build("forward_harness_san", ["-O1", "-g", "-DJBF_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"])
+    exe = build_source(SRC, "forward_harness_san", ["-pthread", "-O1", "-g", "-DJBF_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"])
     p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     text = p.stdout.decode("utf-8", "replace")
     assert p.returncode == 0 and "all ok" in text and "MISMATCH" not in text and "runtime error" not in text, text

@@ -1,7 +1,7 @@
 """The contact pass on the GPU (jb_contacts_device / jb_contacts; jb_contacts_kernel in jitterbug_amd/csrc/jb_api.hip, per-slot function
 jb_contacts.hpp): every family through a snapshot stack against the oracle's contact lists under the bounds of the fp32 host build
 (tests/contacts_inputs.py: three times the host's measured worst, per block and family); consistency with the forward pass; the shapes at
-which the indexing can go wrong, bit for bit; the state, the counters and the solver statistics left untouched; the refusals.
+which the indexing can go wrong, bit for bit; the state, the counters and the solver statistics left untouched (the refusals: tests/test_gpu_pass_refusals.py).
 
 The kernel gives a wave to four env-states (a quad of lanes each, three mirror groups): N = 1 is one quad with the rest of its wave
 repeating it, N = 5 a full wave plus a ragged one, and a stack of snapshots starts a new wave at every snapshot."""
@@ -203,32 +203,4 @@ def test_the_pass_does_not_touch_the_state_the_counters_or_the_solver_statistics
     for a, b in zip(counters, env.counters()):
         assert np.array_equal(a, b)
     assert env.solver_stats() == stats
-    env.close()
-
-
-# ------------------------------------------------------------------------------------------------ (d) refusals
-def test_refusals_launch_nothing():
-    torch = _torch()
-    env = make_env(5)
-    L, h = env._L, env._h
-    buf = torch.full((5 * model.NGEOM * 3,), -7.25, device=torch.device("cuda", 0), dtype=torch.float32)
-    torch.cuda.synchronize()
-    p = buf.data_ptr()
-    assert L.jb_contacts_device(h, None, 0, None, None, None, p, None) == -1 and b"n_snaps" in L.jb_last_error()
-    assert L.jb_contacts_device(h, None, -3, None, None, None, p, None) == -1
-    assert L.jb_contacts_device(h, None, 2, None, None, None, p, None) == -1 and b"ONE state" in L.jb_last_error()
-    assert L.jb_contacts_device(h, None, 1, None, None, None, None, None) == -1 and b"NULL" in L.jb_last_error()
-    assert L.jb_contacts(h, None, None, None, None, None) == -1 and b"NULL" in L.jb_last_error()
-    env.step_async(np.zeros(5, dtype=np.float32))
-    assert L.jb_contacts_device(h, None, 1, None, None, None, p, None) == -1 and b"pending" in L.jb_last_error()
-    host = np.full((5, model.NGEOM, 3), -7.25, dtype=np.float32)
-    assert L.jb_contacts(h, None, None, None, _lib.ptr(host), None) == -1 and b"pending" in L.jb_last_error()
-    env.step_wait()
-    env.synchronize()
-    assert (buf == -7.25).all().item() and (host == -7.25).all()
-    assert L.jb_contacts_device(h, None, 1, None, None, None, p, None) == 0
-    env.synchronize()
-    assert torch.isfinite(buf).all().item() and not (buf == -7.25).any().item()
-    env.release_staging()
-    assert np.isfinite(env.contacts()["geom_frc"]).all()
     env.close()

@@ -1,7 +1,7 @@
 """The forward-dynamics pass on the GPU (jb_forward_device / jb_forward; jb_forward_kernel in jitterbug_amd/csrc/jb_api.hip, element function
 jb_forward.hpp): every output against the oracle under the bounds of the fp32 host build (tests/forward_inputs.py: three times the host's
 measured worst, per output block); the shapes at which the indexing can go wrong, bit for bit; the state, the counters and the solver
-statistics left untouched; agreement with the step kernel's own first substep; the refusals; the Python surface.
+statistics left untouched; agreement with the step kernel's own first substep; the Python surface (the refusals: tests/test_gpu_pass_refusals.py).
 
 The kernel gives a wave to four env-states (a quad of lanes each, three mirror groups): N = 1 is one quad with the rest of its wave
 repeating it, N = 5 a full wave plus a ragged one, and a stack of snapshots starts a new wave at every snapshot."""
@@ -251,32 +251,7 @@ def test_qacc_is_what_one_step_of_one_substep_leaves_in_the_warm_start(variant):
     env.close()
 
 
-# ------------------------------------------------------------------------------------------------ (e) refusals
-def test_refusals_launch_nothing():
-    torch = _torch()
-    env = make_env(5)
-    L, h = env._L, env._h
-    buf = torch.full((5 * 15,), -7.25, device=torch.device("cuda", 0), dtype=torch.float32)
-    torch.cuda.synchronize()
-    p = buf.data_ptr()
-    assert L.jb_forward_device(h, None, 0, None, p, None, None, None, None) == -1 and b"n_snaps" in L.jb_last_error()
-    assert L.jb_forward_device(h, None, -3, None, p, None, None, None, None) == -1
-    assert L.jb_forward_device(h, None, 2, None, p, None, None, None, None) == -1 and b"ONE state" in L.jb_last_error()
-    assert L.jb_forward_device(h, None, 1, None, None, None, None, None, None) == -1 and b"NULL" in L.jb_last_error()
-    assert L.jb_forward(h, None, None, None, None, None, None) == -1 and b"NULL" in L.jb_last_error()
-    env.step_async(np.zeros(5, dtype=np.float32))
-    assert L.jb_forward_device(h, None, 1, None, p, None, None, None, None) == -1 and b"pending" in L.jb_last_error()
-    host = np.full((5, 15), -7.25, dtype=np.float32)
-    assert L.jb_forward(h, None, _lib.ptr(host), None, None, None, None) == -1 and b"pending" in L.jb_last_error()
-    env.step_wait()
-    env.synchronize()
-    assert (buf == -7.25).all().item() and (host == -7.25).all()
-    assert L.jb_forward_device(h, None, 1, None, p, None, None, None, None) == 0
-    env.synchronize()
-    assert torch.isfinite(buf).all().item()
-    env.release_staging()
-    assert np.isfinite(env.forward()["qacc"]).all()
-    env.close()
+# (refusals: tests/test_gpu_pass_refusals.py, one test for the three passes)
 
 
 # ------------------------------------------------------------------------------------------------ (f) surface

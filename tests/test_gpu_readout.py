@@ -1,12 +1,11 @@
 """The readout pass on the GPU (jb_readout_device / jb_readout; jitterbug_amd/csrc/jb_readout.hpp): every output against the oracle at the
 state get_state returns, under the bounds of the fp32 host build (tests/readout_inputs.py); a stack of snapshots against single calls and
-an env of a batch against the same state alone, bit for bit; absent outputs; the state left untouched; the refusals.
+an env of a batch against the same state alone, bit for bit; absent outputs; the state left untouched (the refusals: tests/test_gpu_pass_refusals.py).
 
 The kernel gives a quad of lanes to an env-state and 16 env-states to a block: N = 17 is one block plus one, N = 64 four whole blocks."""
 import numpy as np
 import pytest
 
-from jitterbug_amd import _lib, model
 from tests import readout_inputs as ri
 
 pytestmark = pytest.mark.gpu
@@ -163,28 +162,3 @@ def test_the_pass_does_not_touch_the_state():
         e.synchronize()
     assert np.array_equal(bits(rows[0]), bits(rows[1]))
     env.close(); twin.close()
-
-
-def test_refusals_launch_nothing():
-    torch = _torch()
-    env = make_env(17)
-    L, h = env._L, env._h
-    buf = torch.full((17 * ri.NF * 12,), -7.25, device=torch.device("cuda", 0), dtype=torch.float32)
-    torch.cuda.synchronize()
-    p = buf.data_ptr()
-    assert L.jb_readout_device(h, None, 0, p, None, None, None) == -1 and b"n_snaps" in L.jb_last_error()
-    assert L.jb_readout_device(h, None, -3, p, None, None, None) == -1
-    assert L.jb_readout_device(h, None, 1, None, None, None, None) == -1 and b"NULL" in L.jb_last_error()
-    assert L.jb_readout(h, None, None, None, None) == -1 and b"NULL" in L.jb_last_error()
-    env.step_async(np.zeros(17, dtype=np.float32))
-    assert L.jb_readout_device(h, None, 1, p, None, None, None) == -1 and b"pending" in L.jb_last_error()
-    host = np.full((17, ri.NF, 12), -7.25, dtype=np.float32)
-    assert L.jb_readout(h, _lib.ptr(host), None, None, None) == -1 and b"pending" in L.jb_last_error()
-    env.step_wait()
-    env.synchronize()
-    assert (buf == -7.25).all().item() and (host == -7.25).all()
-    assert L.jb_readout_device(h, None, 1, p, None, None, None) == 0
-    env.synchronize()
-    assert torch.isfinite(buf).all().item()
-    assert model.NFRAME == 33
-    env.close()

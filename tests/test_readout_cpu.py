@@ -12,25 +12,16 @@ import numpy as np
 import pytest
 
 from jitterbug_amd import model
+from tests.build_harness import build_source
 from tests import readout_inputs as ri
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "readout_harness.cpp")
-CSRC = os.path.join(HERE, "..", "jitterbug_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("jb_readout.hpp", "jb_snapshot.hpp", "jb_sim.hpp", "jb_lane.hpp", "jb_model_build.hpp", "jb_default_params.h")]
-
-
-def _build(out_name, extra):
-    out = os.path.join(HERE, "_build", out_name)
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not (os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in DEPS)):
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wno-unknown-pragmas"] + extra + ["-o", out, SRC])
-    return out
 
 
 @pytest.fixture(scope="module")
 def hr():
-    lib = C.CDLL(_build("libjb_readout_host.so", ["-O2", "-fPIC", "-shared"]))
+    lib = C.CDLL(build_source(SRC, "libjb_readout_host.so", ["-Wall", "-O2", "-fPIC", "-shared"]))
     vp = C.c_void_p
     lib.jbr_run_f32.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     lib.jbr_run_f64.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
@@ -119,7 +110,7 @@ def test_host_code_under_address_and_undefined_sanitizers():
     """The one sanitizer run of this code: a stand-alone program (its own main, tests/readout_harness.cpp -DJBR_MAIN) over ragged sizes,
     absent outputs and a 3-snapshot stack, on heap blocks of exactly the promised sizes."""
     # (the sanitizer runtimes are linked statically: the program is complete in itself, whatever else the process environment loads)
-    exe = _build("readout_harness_san", ["-O1", "-g", "-DJBR_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"])
+    exe = build_source(SRC, "readout_harness_san", ["-Wall", "-O1", "-g", "-DJBR_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"])
     p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
     text = p.stdout.decode("utf-8", "replace")
     assert p.returncode == 0 and "all ok" in text and "MISMATCH" not in text and "runtime error" not in text, text

@@ -8,23 +8,16 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.build_harness import build_source
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "snapshot_harness.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "jitterbug_amd", "csrc", f) for f in ("jb_snapshot.hpp", "jb_lane.hpp")]
 ROOT_F, LEG_F, WORDS = 32, 6, 58
-
-
-def _build(out_name, extra):
-    out = os.path.join(HERE, "_build", out_name)
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not (os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in DEPS)):
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wno-unknown-pragmas"] + extra + ["-o", out, SRC])
-    return out
 
 
 @pytest.fixture(scope="module")
 def hs():
-    lib = C.CDLL(_build("libjb_snapshot_host.so", ["-O2", "-fPIC", "-shared"]))
+    lib = C.CDLL(build_source(SRC, "libjb_snapshot_host.so", ["-Wall", "-O2", "-fPIC", "-shared"]))
     vp = C.c_void_p
     lib.jbs_fork.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
     lib.jbs_fork.restype = None
@@ -168,7 +161,7 @@ def test_host_code_under_address_and_undefined_sanitizers():
     """The one sanitizer run of this code: a stand-alone program (its own main, tests/snapshot_harness.cpp -DJBS_MAIN) over the ragged,
     fan-out and clamped cases, on heap blocks of exactly the promised sizes."""
     # (the sanitizer runtimes are linked statically: the program is complete in itself, whatever else the process environment loads)
-    exe = _build("snapshot_harness_san", ["-O1", "-g", "-DJBS_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"])
+    exe = build_source(SRC, "snapshot_harness_san", ["-Wall", "-O1", "-g", "-DJBS_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"])
     p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
     text = p.stdout.decode("utf-8", "replace")
     assert p.returncode == 0 and "all ok" in text and "MISMATCH" not in text and "runtime error" not in text, text
