@@ -276,6 +276,7 @@ __device__ __forceinline__ void step_body(KArgs a, StepIO io) {
     else { scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds; }
     scr.ovc_stride = MAIN;
     scr.pd = LAY.pd;
+    scr.stage_major = LAY.stage_major; scr.term_major = LAY.term_major;
     scr.aux_lane = aux_on && grp >= 2;
 #ifdef JB_WAVE_STATS
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
@@ -511,6 +512,7 @@ struct PassWave {
         scr.ovc = lds + SC_OVC * MAIN + lane_in_grp; scr.pd2 = LAY.pd2; scr.red_lds = LAY.red_lds;
         scr.ovc_stride = MAIN;
         scr.pd = LAY.pd;
+        scr.stage_major = LAY.stage_major; scr.term_major = LAY.term_major;
         scr.aux_lane = LAY.aux && grp >= 2;
         v = f.first;
         v.root += (long long)k * f.stride_words; v.leg += (long long)k * f.stride_words;

@@ -99,6 +99,27 @@ JB_D float row_transpose_sum(float v0, float v1, float v2, float v3) {
     auto r = __builtin_amdgcn_permlane16_swap(b(s02), b(s13), false, false);
     return f(r[0]) + f(r[1]);
 }
+// The same sum in its two stages, for a caller that reduces SEVERAL quadruples (jb_sim.hpp contact_sweep, StepLayout::stage_major): a swap
+// must not read a register a VALU instruction wrote in the two cycles before it, so a quadruple reduced on its own waits between each add
+// and the swap that takes its result (s_nop 1, twice per quadruple: tools/asm_wait_states.py).  Stage-major - the first swaps of a
+// batch, their adds, the second swaps, their adds - puts another quadruple's instructions there.  Every total is formed by the same three
+// adds on the same operands: the same bits.
+struct RowHalves { float a0, a1, b0, b1; };      // after the first swaps: s02 = a0 + a1, s13 = b0 + b1
+struct RowRows { float c0, c1; };                // after the second swap: the total = c0 + c1
+JB_D RowHalves row_transpose_swap1(float v0, float v1, float v2, float v3) {
+    auto f = [](unsigned u) { return __builtin_bit_cast(float, u); };
+    auto b = [](float x) { return __builtin_bit_cast(unsigned, x); };
+    auto r02 = __builtin_amdgcn_permlane32_swap(b(v0), b(v2), false, false);
+    auto r13 = __builtin_amdgcn_permlane32_swap(b(v1), b(v3), false, false);
+    return RowHalves{f(r02[0]), f(r02[1]), f(r13[0]), f(r13[1])};
+}
+JB_D void row_transpose_add1(const RowHalves& h, float& s02, float& s13) { s02 = h.a0 + h.a1; s13 = h.b0 + h.b1; }
+JB_D RowRows row_transpose_swap2(float s02, float s13) {
+    auto f = [](unsigned u) { return __builtin_bit_cast(float, u); };      // (by value: a bit cast applied to the vector ELEMENT r[1] itself reads element 0)
+    auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, s02), __builtin_bit_cast(unsigned, s13), false, false);
+    return RowRows{f(r[0]), f(r[1])};
+}
+JB_D float row_transpose_add2(const RowRows& r) { return r.c0 + r.c1; }
 // The value lane L ^ off holds (off = 32, 16 or 8: the distance to the lane group two groups on).  Exact for the lanes of the LOWER
 // group of each pair (what jb_sim.hpp's aux bodies need: groups 0 / 1 read groups 2 / 3); the upper group's result is unspecified.
 JB_D unsigned xor_get_bits(unsigned u, int off) {
@@ -329,6 +350,34 @@ template <typename T> inline Quad<T> row_transpose_sum(const Quad<T>& v0, const 
     w->barrier();
     return r;
 }
+// ... and its two stages as the device has them: after the first swaps row g holds, of value (g & 2 ? 2 : 0) and of value (g & 2 ? 3 : 1),
+// the shares of groups (g & 1) and (g & 1) + 2; after the second an even row holds the two partial sums of its first value, an odd row
+// those of its second.  Four groups only (the one caller's condition).
+template <typename T> struct QuadHalves { Quad<T> a0, a1, b0, b1; };
+template <typename T> struct QuadRows { Quad<T> c0, c1; };
+template <typename T> inline QuadHalves<T> row_transpose_swap1(const Quad<T>& v0, const Quad<T>& v1, const Quad<T>& v2, const Quad<T>& v3) {
+    HostWave* w = g_host_wave;
+    const Quad<T>* v[4] = {&v0, &v1, &v2, &v3};
+    const int g = g_host_grp, lo = g & 1, hi = lo + 2, x = (g & 2) ? 2 : 0, y = x + 1;
+    for (int k = 0; k < 4; k++) for (int i = 0; i < 4; i++) w->mbox[g][k][i] = (double)v[k]->v[i];
+    w->barrier();
+    QuadHalves<T> h;
+    for (int i = 0; i < 4; i++) { h.a0.v[i] = (T)w->mbox[lo][x][i]; h.a1.v[i] = (T)w->mbox[hi][x][i]; h.b0.v[i] = (T)w->mbox[lo][y][i]; h.b1.v[i] = (T)w->mbox[hi][y][i]; }
+    w->barrier();
+    return h;
+}
+template <typename T> inline void row_transpose_add1(const QuadHalves<T>& h, Quad<T>& s02, Quad<T>& s13) { s02 = h.a0 + h.a1; s13 = h.b0 + h.b1; }
+template <typename T> inline QuadRows<T> row_transpose_swap2(const Quad<T>& s02, const Quad<T>& s13) {
+    HostWave* w = g_host_wave;
+    const int g = g_host_grp, even = g & ~1, k = g & 1;
+    for (int i = 0; i < 4; i++) { w->mbox[g][0][i] = (double)s02.v[i]; w->mbox[g][1][i] = (double)s13.v[i]; }
+    w->barrier();
+    QuadRows<T> r;
+    for (int i = 0; i < 4; i++) { r.c0.v[i] = (T)w->mbox[even][k][i]; r.c1.v[i] = (T)w->mbox[even + 1][k][i]; }
+    w->barrier();
+    return r;
+}
+template <typename T> inline Quad<T> row_transpose_add2(const QuadRows<T>& r) { return r.c0 + r.c1; }
 template <typename T> inline Quad<T> xor_sum(const Quad<T>& x, int off, bool) {
     if (!g_host_wave) return x;
     return x + host_exchange(x, g_host_grp ^ (off / g_host_wave->gstride));

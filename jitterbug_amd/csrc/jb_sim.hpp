@@ -428,6 +428,8 @@ template <typename V> struct LaneScratch {
     int pd2;                  // the thread pair contact's frame (9 values): sc.ovc[(pd2 + i) * ovc_stride] - behind the overflow candidates, in LDS (SC_PD2 - SC_OVC) or, in the LEAN variant, in global memory (rare path: 0.2 % of the robots)
     bool aux_lane = false;    // this lane is an AUX lane (SimOpts::aux): it runs phase A on a body of its own and must not write the scratch of the leg it mirrors
     bool red_lds;             // the group reduction hands its totals over through SC_RED (false: combined in registers, the LEAN variant has no room for the buffer)
+    bool stage_major = false; // the transposed group reduction runs stage by stage over batches of quadruples (StepLayout::stage_major); false: one quadruple after the other
+    bool term_major = false;  // the packed accumulations of a contact run term by term over all their accumulators (StepLayout::term_major); false: one accumulator after the other
     JB_HD V ld(int i) const { return p[i * stride]; }
     JB_HD void st(int i, const V& v) const { p[i * stride] = v; }
     JB_HD V ldv(const typename lane_traits<V>::uint& i) const { return ld_gather(p, stride, i); }      // per-lane index
@@ -824,7 +826,20 @@ JB_HD void row_pairs(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const V& lin,
     }
 }
 // residuals rho_k = B_k y - ahat_k of the three rows at the iterate (root part as row pairs, then the two joint columns)
-template <typename V> JB_HD void row_residuals(const RowPairs<V>& R, const Pk2<V> (&yr)[3], const Pk2<V>& yj, V (&rho)[3]) {
+template <typename V> JB_HD void row_residuals(const RowPairs<V>& R, const Pk2<V> (&yr)[3], const Pk2<V>& yj, V (&rho)[3], const bool term_major = false) {
+    if (term_major) {      // (like acc_root: the three rows take turns, no row's multiply-add follows its own)
+        Pk2<V> t[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) t[k] = R.b[k][0] * yr[0];
+#pragma unroll
+        for (int q = 1; q < 4; q++) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) t[k] = t[k] + R.b[k][q] * (q < 3 ? yr[q] : yj);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) rho[k] = (pk_lo(t[k]) - R.ah[k]) + pk_hi(t[k]);
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         Pk2<V> t = R.b[k][0] * yr[0];
@@ -852,8 +867,26 @@ JB_HD void weighted_rows(const RowPairs<V>& R, const V& D, const V& mu, const V&
 template <typename V> JB_HD V wb_get(const WeightedRows<V>& Q, int k, int c) { return pk_half(Q.wb[k][c >> 1], c & 1); }
 template <typename V> JB_HD V rb_get(const RowPairs<V>& R, int k, int c) { return pk_half(R.b[k][c >> 1], c & 1); }
 // the root block's share  A += B^T W B,  rr += B^T W ahat : pairs of rows of B^T (= column pairs of B) times single elements of W B
-template <typename V> JB_HD void acc_root(const RowPairs<V>& R, const WeightedRows<V>& Q, NewtonAcc<V>& acc) {
+template <typename V> JB_HD void acc_root(const RowPairs<V>& R, const WeightedRows<V>& Q, NewtonAcc<V>& acc, const bool term_major = false) {
     using W = Pk2<V>;
+    if (term_major) {
+        // Term-major (StepLayout::term_major): term k of EVERY accumulator, then term k + 1.  A packed result read by the very next instruction
+        // costs a wait state, and an accumulator's three fused multiply-adds in a row (fma3) are exactly that; fifteen accumulators taking
+        // turns leave none.  Each accumulator still gets its three terms in the order 0, 1, 2 with the same contraction: the same bits
+        // (tests/test_stage_major_cpu.py).
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+                const W w = W(wb_get(Q, k, j));
+#pragma unroll
+                for (int ip = j / 2; ip < 3; ip++) acc.A.p[s6p(ip, j)] = acc.A.p[s6p(ip, j)] + R.b[k][ip] * w;
+            }
+#pragma unroll
+            for (int ip = 0; ip < 3; ip++) acc.rr[ip] = acc.rr[ip] + R.b[k][ip] * W(Q.wa[k]);
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 6; j++) {
         const W w0 = W(wb_get(Q, 0, j)), w1 = W(wb_get(Q, 1, j)), w2 = W(wb_get(Q, 2, j));
@@ -880,7 +913,7 @@ template <typename V> JB_HD V col_times_wa(const RowPairs<V>& R, const WeightedR
 // line search's phi' and phi'' at y + ld->alpha * (ld's direction).
 template <typename V, bool PAIR = false, bool LS = false>
 JB_HD void contact_apply(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const V& mu, int slot, bool lane_on, int mode,
-                         const Pk2<V> (&yr)[3], const V (&yl)[2], const V& ym, NewtonAcc<V>& acc, const LineDir<V>* ld = nullptr) {
+                         const Pk2<V> (&yr)[3], const V (&yl)[2], const V& ym, NewtonAcc<V>& acc, const LineDir<V>* ld = nullptr, const bool term_major = false) {
     using U = typename lane_traits<V>::uint;
     using W = Pk2<V>;
     const int level = slot_level(slot);
@@ -892,7 +925,7 @@ JB_HD void contact_apply(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const V& 
     const V y7 = has_kn ? yl[1] : ym;              // levels 0/1 have a zero column 7
     RowPairs<V> R;
     row_pairs<V, PAIR>(rv, dk, lin, rv.jsh, rv.j7, rv.ah, R);
-    row_residuals<V>(R, yr, W(yl[0], y7), rho);
+    row_residuals<V>(R, yr, W(yl[0], y7), rho, term_major);
     const auto valid = gt(D, V(0));
     if (LS && mode == 3) {
         const V d7 = has_kn ? ld->dl[1] : ld->dm;
@@ -929,7 +962,7 @@ JB_HD void contact_apply(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const V& 
     V f1 = sel(a1, V(1), V(0)), f2 = sel(a2, V(1), V(0)), f3 = sel(a3, V(1), V(0)), f4 = sel(a4, V(1), V(0));
     WeightedRows<V> Q;
     weighted_rows<V>(R, D, mu, f1, f2, f3, f4, Q);
-    acc_root<V>(R, Q, acc);
+    acc_root<V>(R, Q, acc, term_major);
     if (has_sh) {
 #pragma unroll
         for (int ip = 0; ip < 3; ip++) acc.B[ip][0] = col_times_wb<V>(R, Q, 6, ip, acc.B[ip][0]);
@@ -1028,7 +1061,7 @@ template <typename V> JB_HD typename lane_traits<V>::uint quad_seg_sum_u(const t
 // of the iterate of leg it.src.
 template <typename V, bool LS = false>
 JB_HD void contact_apply_leg(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const V& mu, const SpreadItem<V>& it, int mode,
-                             const Pk2<V> (&yr)[3], const V (&yl)[2], NewtonAcc<V>& acc, const LineDir<V>* ld = nullptr, const V* dls = nullptr) {
+                             const Pk2<V> (&yr)[3], const V (&yl)[2], NewtonAcc<V>& acc, const LineDir<V>* ld = nullptr, const V* dls = nullptr, const bool term_major = false) {
     using U = typename lane_traits<V>::uint;
     using MK = typename lane_traits<V>::mask;
     using W = Pk2<V>;
@@ -1043,7 +1076,7 @@ JB_HD void contact_apply_leg(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const
         for (int k = 0; k < 3; k++) { jsh[k] = sel(it.valid, rv.jsh[k], V(0)); j7[k] = sel(it.valid, rv.j7[k], V(0)); ah[k] = sel(it.valid, rv.ah[k], V(0)); }
         row_pairs<V, false>(rv, dk, V(1), jsh, j7, ah, R);
     }
-    row_residuals<V>(R, yr, W(yl[0], yl[1]), rho);
+    row_residuals<V>(R, yr, W(yl[0], yl[1]), rho, term_major);
     const MK valid = gt(D, V(0));
     if (LS && mode == 3) {      // line search (see contact_apply); dls: the joint part of the direction for leg it.src
         const W dq[3] = {W(ld->dr[0], ld->dr[1]), W(ld->dr[2], ld->dr[3]), W(ld->dr[4], ld->dr[5])};
@@ -1074,7 +1107,7 @@ JB_HD void contact_apply_leg(const RowVals<V>& rv, const Vec3<V> (&dk)[3], const
     V f1 = sel(a1, V(1), V(0)), f2 = sel(a2, V(1), V(0)), f3 = sel(a3, V(1), V(0)), f4 = sel(a4, V(1), V(0));
     WeightedRows<V> Q;
     weighted_rows<V>(R, D, mu, f1, f2, f3, f4, Q);
-    acc_root<V>(R, Q, acc);
+    acc_root<V>(R, Q, acc, term_major);
     // the leg block of leg it.src: computed here, added in the lane of that leg
     const V m0 = sel(k0, V(1), V(0)), m1 = sel(k1, V(1), V(0)), m2 = sel(k2, V(1), V(0)), m3 = sel(k3, V(1), V(0));
     const V Z = V(0);
@@ -1375,8 +1408,8 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
             if (LS && mode == 3) {
                 V dls[2];
                 dls[0] = ld_leg(sc.p, sc.stride, zero_u<V>() + (unsigned)(box + 6), it.src, me); dls[1] = ld_leg(sc.p, sc.stride, zero_u<V>() + (unsigned)(box + 7), it.src, me);
-                contact_apply_leg<V, LS>(rv, dk, mu, it, 3, yr, yls, acc, &ldir, dls);
-            } else contact_apply_leg<V, LS>(rv, dk, mu, it, mode, yr, yls, acc);
+                contact_apply_leg<V, LS>(rv, dk, mu, it, 3, yr, yls, acc, &ldir, dls, sc.term_major);
+            } else contact_apply_leg<V, LS>(rv, dk, mu, it, mode, yr, yls, acc, nullptr, nullptr, sc.term_major);
             spread_rounds = r + 1;
             if (!any_lane(it.more)) break;
         }
@@ -1411,7 +1444,7 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
             const int c0 = 4 * (rank - ROW_K) * sc.ovc_stride;
             row_values<V, PAIR>(m, sc, xtra, slot, v3<V>(sc.ovc[c0], sc.ovc[c0 + sc.ovc_stride], sc.ovc[c0 + 2 * sc.ovc_stride]), sc.ovc[c0 + 3 * sc.ovc_stride], rv);
         }
-        contact_apply<V, PAIR, LS>(rv, dk, mu, slot, lane_on, mode, yr, yl, ym, acc, (LS && mode == 3) ? &ldir : nullptr);
+        contact_apply<V, PAIR, LS>(rv, dk, mu, slot, lane_on, mode, yr, yl, ym, acc, (LS && mode == 3) ? &ldir : nullptr, sc.term_major);
     }
     if (LS && mode == 3) {      // the env's totals on every lane: over the legs, then over the lane groups
         acc.ls_g = quad_sum(acc.ls_g); acc.ls_h = quad_sum(acc.ls_h); acc.ls_a = quad_sum(acc.ls_a);
@@ -1419,7 +1452,12 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
         return spread_rounds + 8 * rest_rounds;
     }
     if (plan.grouped) {
-        acc.bw0 = group_sum_u<V>(sc, acc.bw0); acc.bw1 = group_sum_u<V>(sc, acc.bw1); acc.xh = group_sum_u<V>(sc, acc.xh);
+        if (sc.stage_major && sc.ngrp == 4) {      // (the three records' butterflies stage by stage, like the totals below)
+            acc.bw0 = xor_sum_u(acc.bw0, 2 * sc.gstride, false); acc.bw1 = xor_sum_u(acc.bw1, 2 * sc.gstride, false); acc.xh = xor_sum_u(acc.xh, 2 * sc.gstride, false);
+            acc.bw0 = xor_sum_u(acc.bw0, sc.gstride, true); acc.bw1 = xor_sum_u(acc.bw1, sc.gstride, true); acc.xh = xor_sum_u(acc.xh, sc.gstride, true);
+        } else {
+            acc.bw0 = group_sum_u<V>(sc, acc.bw0); acc.bw1 = group_sum_u<V>(sc, acc.bw1); acc.xh = group_sum_u<V>(sc, acc.xh);
+        }
         if (mode == 0 && sc.ngrp == 4 && sc.gstride == 16 && sc.red_lds) {
             // Only the main lanes need the totals: reduce four values at a time so that row (= group) g ends with the total
             // of value 4k+g, hand the totals over through the scratch (the overflow row entries are dead here) and let the
@@ -1429,8 +1467,33 @@ JB_HD int contact_sweep(const LaneModel<V>& m, const LaneScratch<V>& sc, bool xt
             acc_pack(acc, v);
             if (PAIR) { v[52] = acc.X; v[53] = V(0); v[54] = V(0); v[55] = V(0); }
             static_assert(4 * NQ4 <= 56, "reduction buffer");
+            constexpr int RED_BATCH = 4;              // quadruples in flight in the stage-major form (the register budget: tools/experiments/wait_states.txt)
+            if (sc.stage_major) {
+                // Stage-major: a batch's first swaps, their adds, its second swaps, their adds and stores.  A quadruple on its own is swap, swap,
+                // add, add, swap, add with each swap waiting for the add in front of it; in a batch another quadruple's instruction stands
+                // there (the machine scheduler keeps the stated order; with JB_SCHED_FENCE() between the stages the same listing ran slower:
+                // tools/experiments/wait_states.txt).  Batches of at most RED_BATCH, of
+                // nearly equal size (13: 4 3 3 3; PAIR's 14: 4 3 4 3) - the whole set at once would hold all 52 values twice.
+                constexpr int NB = (NQ4 + RED_BATCH - 1) / RED_BATCH;
 #pragma unroll
-            for (int k = 0; k < NQ4; k++) sc.st(SC_RED + 4 * k + sc.grp, row_transpose_sum(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]));
+                for (int b = 0; b < NB; b++) {
+                    const int k0 = (b * NQ4 + NB - 1) / NB, k1 = ((b + 1) * NQ4 + NB - 1) / NB;
+                    decltype(row_transpose_swap1(v[0], v[0], v[0], v[0])) h[RED_BATCH];
+                    decltype(row_transpose_swap2(v[0], v[0])) r[RED_BATCH];
+                    V s02[RED_BATCH], s13[RED_BATCH];
+#pragma unroll
+                    for (int k = k0; k < k1; k++) h[k - k0] = row_transpose_swap1(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+#pragma unroll
+                    for (int k = k0; k < k1; k++) row_transpose_add1(h[k - k0], s02[k - k0], s13[k - k0]);
+#pragma unroll
+                    for (int k = k0; k < k1; k++) r[k - k0] = row_transpose_swap2(s02[k - k0], s13[k - k0]);
+#pragma unroll
+                    for (int k = k0; k < k1; k++) sc.st(SC_RED + 4 * k + sc.grp, row_transpose_add2(r[k - k0]));
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < NQ4; k++) sc.st(SC_RED + 4 * k + sc.grp, row_transpose_sum(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]));
+            }
             wave_sync();          // every group's totals are in the scratch
             // Every lane reloads (the scratch addresses are mirrored per group: the same words the main lanes read).  The other groups' partial
             // sums are dead from here on - nobody reads their star_solve - and a reload under the group predicate would keep all of them alive

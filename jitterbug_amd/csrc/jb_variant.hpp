@@ -37,6 +37,16 @@ struct StepLayout {
                              // lane (jb_lane.hpp main_vote, SimOpts::scalar_votes, tools/experiments/scalar_votes.txt); false: under the main lanes'
                              // predicate and fetched back from the first lane - the rows that would gain a hot scratch operation or lose occupancy,
                              // and every row with -DJB_VECTOR_VOTES (today no row objects).  Same bits.
+    bool stage_major;        // the transposed group reduction of a full Newton sweep runs its quadruples in batches, stage by stage (LaneScratch::stage_major,
+                             // jb_sim.hpp contact_sweep, tools/experiments/wait_states.txt): an add is followed by another quadruple's swap, not by the
+                             // wait states in front of its own.  Only the rows that take that reduction - four lane groups 16 lanes apart, the totals
+                             // handed over through the scratch - have the choice, and the PAIR row among them keeps the old order: with both new orders
+                             // its hot part grows by two instructions, with the term-major one alone it is shortest.  False everywhere with
+                             // -DJB_ELEMENT_MAJOR_ORDER, the reference form.  Same bits.
+    bool term_major;         // the packed accumulations of a contact - the root block's fifteen accumulators (jb_sim.hpp acc_root), the three rows' residuals
+                             // (row_residuals) - run term by term over all accumulators, so that no packed multiply-add reads the result of the one in
+                             // front of it (LaneScratch::term_major); false: one accumulator after the other - the one row whose hot part the new order
+                             // gives scratch operations, and every row with -DJB_ELEMENT_MAJOR_ORDER.  Same bits.
     bool late_env_index;     // the kernel's closing stores form their addresses from a fresh copy of the env index, so that no byte offset of the
                              // entry's loads stays in registers through the loops (jb_api.hip step_body); it comes with the scalar votes - whose
                              // flagship row would otherwise spill that offset once per launch - except on the one row it gives hot scratch operations
@@ -64,6 +74,12 @@ constexpr StepLayout step_layout(int epw, bool lean, bool pair) {
     l.scalar_votes = false;
 #else
     l.scalar_votes = true;
+#endif
+#ifdef JB_ELEMENT_MAJOR_ORDER
+    l.stage_major = false; l.term_major = false;
+#else
+    l.stage_major = l.groups == 4 && l.main_lanes == 16 && l.red_lds && !pair;
+    l.term_major = !(pair && !lean && epw == 8);
 #endif
     l.late_env_index = l.scalar_votes && !(pair && !lean && epw == 8);
     return l;
@@ -121,7 +137,7 @@ template <typename V> JB_HD void bind_scratch(LaneScratch<V>& sc, const StepLayo
     sc.p = base; sc.stride = stride;
     sc.grp = grp; sc.ngrp = l.groups; sc.gstride = l.main_lanes;
     sc.ovc = l.red_lds ? base + SC_OVC * stride : ext_ovc; sc.ovc_stride = stride;
-    sc.pd = l.pd; sc.pd2 = l.pd2; sc.red_lds = l.red_lds;
+    sc.pd = l.pd; sc.pd2 = l.pd2; sc.red_lds = l.red_lds; sc.stage_major = l.stage_major; sc.term_major = l.term_major;
     sc.aux_lane = l.aux && grp >= 2;
 }
 // the lanes that hold an env's state: the main lanes, their replica and the aux lanes (the other helper lanes only take part in the substeps)

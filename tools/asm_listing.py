@@ -2,8 +2,8 @@
 
     python tools/asm_listing.py [-DJB_DEV_ONLY4 ...] [--line-tables] -o OUT.s
 
-compiles the listing that tools/asm_spills.py, asm_copies.py, asm_exec_regions.py and asm_dpp_forms.py report on (asm_copies.py and
-asm_exec_regions.py name source lines: build theirs with --line-tables); tools/kernel_resources.py compiles with the same flags.  Nothing of it ships.
+compiles the listing that tools/asm_spills.py, asm_copies.py, asm_exec_regions.py, asm_dpp_forms.py and asm_wait_states.py report on (asm_copies.py,
+asm_exec_regions.py and asm_wait_states.py name source lines: build theirs with --line-tables); tools/kernel_resources.py compiles with the same flags.  Nothing of it ships.
 
 parse(path) gives one Function per kernel.  Loops come from backward branches (a label .LBBn_m defined above its s_branch / s_cbranch):
 ONE loop per header label, closed at its LAST back-branch - several back-branches to one header (a `continue`, a rotated latch) are one
