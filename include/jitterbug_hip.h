@@ -355,6 +355,33 @@ int jb_contacts_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n
                        uint8_t* d_unconverged /*[n_snaps*N]*/);
 int jb_contacts(jb_handle* h, const float* ctrl /*[N] nullable*/, float* contact /*[N,JB_NCONTACT,12]*/, int32_t* ncon /*[N]*/, float* geom_frc /*[N,22,3]*/,
                 uint8_t* unconverged /*[N]*/);
+/* Inertia (additive in ABI 5): the terms of the equation of motion  M qacc + bias = passive + actuator + J^T f  in a state, and the
+ * Jacobians of the bodies and the feet - MuJoCo's mj_fullM, qfrc_bias, qfrc_passive, qfrc_actuator, qacc_smooth and mj_jacBodyCom /
+ * mj_jacGeom.  One launch maps a state - the handle's current one, or a stack of snapshots - and an action to them WITHOUT advancing time
+ * and without a substep: nothing but the outputs is written.  Per env-state, in fp32; vectors in MuJoCo's qvel order, as above.
+ *   qM          [15, 15]     the dense symmetric joint-space inertia, both triangles.  An arrow: the 6 x 6 root block, per leg a 6 x 2
+ *                            column pair and a 2 x 2 block, for the motor a 6 x 1 column and a 1 x 1 block; the blocks between two legs
+ *                            and between a leg and the motor are exact zeros, written like every other entry.
+ *   qfrc        [3, 15]      row 0 qfrc_bias: Coriolis, centrifugal and gravity terms; row 1 qfrc_passive: -k theta - b theta' on the
+ *                            eight leg hinges, exact zeros elsewhere; row 2 qfrc_actuator: entry 14 alone (gear * force, the action clamped
+ *                            to the ctrlrange, the force as jb_forward's `motor` has it, its length bias on the unwrapped motor angle)
+ *   qacc_smooth [15]         M^-1 (passive + actuator - bias), the unconstrained acceleration, solved through the arrow.  PLAIN M:
+ *                            jb_forward's qacc carries the implicit damping term h b, this does not.  The relation between the two passes:
+ *                            jb_forward's qfrc_constraint = qM y + h b o y - (passive + actuator - bias), y = jb_forward's qacc.
+ *   jac         [JB_NJAC, 6, 15]  per row block [jacp (3) | jacr (3)] x 15 in world axes.  Blocks 0-9: the ten bodies at their centres of
+ *                            mass, the readout's order (mj_jacBodyCom); block 10 + l: the centre of leg l's foot sphere (geom 7 + 4 l).  The
+ *                            free joint's rotational columns are about the root's own axes through the root origin.  Every entry is
+ *                            written, zeros included.  The other geoms have no block: a point p on body b, r = p - the centre of mass,
+ *                            has jacp(p) = jacp - [r]x jacr with body b's block.
+ * The pass has ONE kernel for every handle, whatever step kernel the handle runs.  The device and the host form and the argument rules are
+ * jb_forward's: d_snaps NULL = the current state (n_snaps 1), d_ctrl [n_snaps * N] or NULL = 0, each output nullable, an absent one costs
+ * no stores, env j takes env j's table, asynchronous on the handle's stream; the result for one env-state does not depend on what else is
+ * in the launch, bit for bit.  JB_E_INVALID, and nothing is launched: n_snaps < 1, d_snaps == NULL with n_snaps != 1, all four outputs
+ * NULL, a jb_step_async pending.  The host form's staging belongs to the handle, only grows, and is freed by jb_release_staging. */
+#define JB_NJAC 14
+int jb_inertia_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_snaps, const float* d_ctrl /*[n_snaps*N] nullable*/, float* d_qM /*[n_snaps*N,15,15]*/,
+                      float* d_qfrc /*[n_snaps*N,3,15]*/, float* d_qacc_smooth /*[n_snaps*N,15]*/, float* d_jac /*[n_snaps*N,JB_NJAC,6,15]*/);
+int jb_inertia(jb_handle* h, const float* ctrl /*[N] nullable*/, float* qM /*[N,15,15]*/, float* qfrc /*[N,3,15]*/, float* qacc_smooth /*[N,15]*/, float* jac /*[N,JB_NJAC,6,15]*/);
 /* seconds each wave of the LAST step launch was alive (one wave = jb_envs_per_wave envs), out[0 .. min(n_waves, max_waves)); returns the
  * number of waves.  Mean against maximum is the load imbalance of the launch (roofline). */
 int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves);

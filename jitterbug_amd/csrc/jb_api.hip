@@ -30,6 +30,7 @@
 #include "jb_nominal_spec.h"
 #include "jb_owned.hpp"
 #include "jb_readout.hpp"
+#include "jb_inertia.hpp"
 #include "jb_sim.hpp"
 #include "jb_snapshot.hpp"
 #include "jb_step.hpp"
@@ -948,6 +949,7 @@ struct jb_handle {
     Dev<float> d_tape, d_rows_stage, d_rew_stage;      // staging of the host-buffer rollouts (jb_step_many, jb_rollout_policy): grow-only
     Dev<unsigned char> d_done_stage;                   // jb_score_tapes_device: the done flags of every step, next to d_rew_stage (grow-only)
     Dev<float> d_readout_stage;                        // jb_readout: the outputs on their way to the host (grow-only)
+    Dev<float> d_inertia_stage;                        // jb_inertia: the actions and the outputs on their way (grow-only)
     Dev<float> d_contacts_stage;                       // jb_contacts: likewise
     Dev<float> d_forward_stage;                        // jb_forward: the actions on their way in, the outputs on their way out (grow-only)
     Dev<uint32_t> d_snap_stage; Dev<int> d_src_stage;  // jb_snapshot / jb_restore: the raw blocks and the index map on their way to / from the host (grow-only)
@@ -1513,7 +1515,7 @@ int jb_release_staging(jb_handle* h) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
     h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset(); h->d_done_stage.reset();
-    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset(); h->d_forward_stage.reset(); h->d_contacts_stage.reset();
+    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset(); h->d_inertia_stage.reset(); h->d_forward_stage.reset(); h->d_contacts_stage.reset();
     return JB_OK;
 }
 // ---------------------------------------------------------------------------------------------- snapshot / restore / fork, tape scoring
@@ -1738,6 +1740,38 @@ int jb_contacts(jb_handle* h, const float* ctrl, float* contact, int32_t* ncon, 
     int rc = check_pass(h, "jb_contacts", nullptr, 1, contact || ncon || geom_frc || unconverged, "four");
     if (!rc) rc = stage_parts(h, h->d_contacts_stage, part, "the contact pass");
     if (!rc) rc = jb_contacts_device(h, nullptr, 1, part[2].dev<float>(), part[0].dev<float>(), part[3].dev<int32_t>(), part[1].dev<float>(), part[4].dev<uint8_t>());
+    return rc ? rc : fetch_parts(h, part);
+}
+// The inertia pass (jb_inertia.hpp): the readout's launch - n_snaps * N env-states, a quad of lanes each, one kernel for every handle; reads
+// the state and the actions, writes only its outputs.
+static_assert(JB_NJAC == IN_NJAC && FW_NV == IN_NV, "the header states the Jacobian's shape");
+int jb_inertia_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, const float* d_ctrl, float* d_qM, float* d_qfrc, float* d_qacc_smooth, float* d_jac) {
+    JB_ENTER(h);
+    InArgs a;
+    int rc = check_pass(h, "jb_inertia_device", d_snaps, n_snaps, d_qM || d_qfrc || d_qacc_smooth || d_jac, "four", &a.first);
+    if (rc) return rc;
+    RoctxRange range("jb_inertia");
+    const int N = h->cfg.n_envs;
+    a.stride_words = (long long)SNAP_WORDS * N;
+    a.total = (long long)n_snaps * N;
+    a.tab = h->ka.lane_model; a.n_tab = h->ka.per_env_model ? N : 1;
+    a.ctrl = d_ctrl;
+    a.qM = d_qM; a.qfrc = d_qfrc; a.qacc = d_qacc_smooth; a.jac = d_jac;
+    a.vec4 = ((((uintptr_t)d_qM | (uintptr_t)d_qfrc | (uintptr_t)d_qacc_smooth | (uintptr_t)d_jac) & 15u) == 0) ? 1 : 0;
+    const long long blocks = (a.total + RO_EPB - 1) / RO_EPB;
+    rc = check_grid("jb_inertia_device", blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL(jb_inertia_kernel, dim3((unsigned)blocks), dim3(64), 0, h->stream, a);
+    JB_HIP(hipGetLastError());
+    return JB_OK;
+}
+int jb_inertia(jb_handle* h, const float* ctrl, float* qM, float* qfrc, float* qacc_smooth, float* jac) {
+    JB_ENTER(h);
+    const size_t F = sizeof(float) * (size_t)h->cfg.n_envs;
+    StagePart part[] = {{jac, F * IN_JAC}, {qM, F * IN_QM}, {qfrc, F * IN_QFRC}, {qacc_smooth, F * IN_QACC}, {const_cast<float*>(ctrl), F, true}};
+    int rc = check_pass(h, "jb_inertia", nullptr, 1, qM || qfrc || qacc_smooth || jac, "four");
+    if (!rc) rc = stage_parts(h, h->d_inertia_stage, part, "the inertia pass");
+    if (!rc) rc = jb_inertia_device(h, nullptr, 1, part[4].dev<float>(), part[1].dev<float>(), part[2].dev<float>(), part[3].dev<float>(), part[0].dev<float>());
     return rc ? rc : fetch_parts(h, part);
 }
 // how long each wave of the last step launch lived, in seconds (s_memrealtime, 100 MHz): out[0 .. n_waves); returns the number of waves

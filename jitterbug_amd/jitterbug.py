@@ -171,6 +171,24 @@ class Physics:
         a[self._i] = float(np.asarray(action, dtype=np.float64).reshape(-1)[0])
         return self._venv.contacts(a, envs=(self._i,))["list"][0]      # (the pass is the batch's; only this env's rows are listed)
 
+    def inertia(self, action=0.0):
+        """This env's terms of the equation of motion under `action`, without advancing time: JitterbugVecEnv.inertia's dict with every
+        output - 'qM' [15, 15], 'qfrc_bias', 'qfrc_passive', 'qfrc_actuator', 'qacc_smooth' [15], 'jac' [14, 6, 15] - float32 in qvel order
+        (the other envs of the batch are evaluated with action 0)."""
+        a = np.zeros(self._venv.num_envs, dtype=np.float32)
+        a[self._i] = float(np.asarray(action, dtype=np.float64).reshape(-1)[0])
+        out = self._venv.inertia(a, qM=True, qfrc=True, qacc_smooth=True, jac=True)
+        return {k: v[self._i].copy() for k, v in out.items()}
+
+    def jacobian(self, name):
+        """(jacp [3, 15], jacr [3, 15]) of `name` in model.JAC_NAMES - a body at its centre of mass (mj_jacBodyCom) or a foot sphere's
+        centre (mj_jacGeom) - in world axes, for this env's current state.  KeyError: no such name.  Every call runs the batch's pass and
+        fetches all its blocks: for several names or envs take JitterbugVecEnv.inertia(jac=True) once and index it by JAC_NAMES."""
+        if name not in model.JAC_NAMES:
+            raise KeyError(name)
+        blk = self._venv.inertia(qM=False, qfrc=False, jac=True)["jac"][self._i, model.JAC_NAMES.index(name)]
+        return blk[0:3].copy(), blk[3:6].copy()
+
     def _contacts(self):
         """the current state's contacts under a zero action, cached like the state"""
         if self._contacts_cache is None or self._contacts_version != self._venv.state_version:

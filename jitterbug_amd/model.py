@@ -52,6 +52,8 @@ NCONTACT, CONTACT_WIDTH = 74, 12
 # rows of a readout's `frames` (jb_readout): the ten bodies, the 22 geoms, the target
 NFRAME = NBODY + NGEOM + 1
 FRAME_GEOM0, FRAME_TARGET = NBODY, NBODY + NGEOM
+# row blocks of an inertia pass's `jac` (jb_inertia): the ten bodies at their centres of mass, then the four foot spheres' centres
+JAC_NAMES = BODY_NAMES + tuple(GEOM_NAMES[g] for g in FOOT_GEOMS)
 
 TASKS = ("move_from_origin", "face_direction", "move_in_direction", "move_to_position", "move_to_pose")
 OBS_DIM = dict(move_from_origin=15, face_direction=16, move_in_direction=19, move_to_position=18, move_to_pose=19)

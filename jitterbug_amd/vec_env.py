@@ -572,6 +572,43 @@ class JitterbugVecEnv:
         _lib.check(self._L.jb_contacts(self._h, _lib.ptr(a), None, None, _lib.ptr(gf), None))
         return gf[:, model.FOOT_GEOMS].copy()
 
+    # ---- inertia: mass matrix, bias / passive / actuator forces, unconstrained acceleration and Jacobians (jb_inertia / jb_inertia_device)
+    def inertia(self, actions=None, qM=True, qfrc=True, qacc_smooth=False, jac=False):
+        """The terms of the equation of motion in the current state under `actions` (None: 0), as a dict of float32 arrays, one row per
+        env (only the outputs asked for); vectors in qvel order [linear, world | angular, root frame | leg hinges | motor]:
+        'qM' [N, 15, 15] the dense joint-space inertia (mj_fullM; both triangles, the blocks between legs exact zeros); 'qfrc_bias',
+        'qfrc_passive', 'qfrc_actuator' [N, 15] each (views of one [N, 3, 15] block): Coriolis + centrifugal + gravity, the leg hinges'
+        springs and dampers, the motor's torque on dof 14; 'qacc_smooth' [N, 15] = qM^-1 (passive + actuator - bias), with PLAIN qM -
+        forward()'s 'qacc' carries the implicit damping h b, and forward()'s 'qfrc_constraint' = qM y + h b o y - (passive + actuator -
+        bias) at y = forward()'s 'qacc'; 'jac' [N, 14, 6, 15]: per block of model.JAC_NAMES (the ten bodies at their centres of mass, the
+        four foot spheres' centres) [jacp (3) | jacr (3)] x 15 in world axes.  A point p of body b has jacp - [p - com]x jacr of b's block.
+        The pass reads the state and never writes it."""
+        n = self.num_envs
+        a = None if actions is None else np.ascontiguousarray(np.broadcast_to(np.asarray(actions, dtype=np.float32).reshape(-1), (n,)))
+        out, f = {}, None
+        if qM:
+            out["qM"] = np.empty((n, model.NV, model.NV), dtype=np.float32)
+        if qfrc:
+            f = np.empty((n, 3, model.NV), dtype=np.float32)
+            out["qfrc_bias"], out["qfrc_passive"], out["qfrc_actuator"] = f[:, 0], f[:, 1], f[:, 2]
+        if qacc_smooth:
+            out["qacc_smooth"] = np.empty((n, model.NV), dtype=np.float32)
+        if jac:
+            out["jac"] = np.empty((n, _lib.NJAC, 6, model.NV), dtype=np.float32)
+        _lib.check(self._L.jb_inertia(self._h, _lib.ptr(a), _lib.ptr(out.get("qM")), _lib.ptr(f), _lib.ptr(out.get("qacc_smooth")), _lib.ptr(out.get("jac"))))
+        return out
+
+    def inertia_device(self, ctrl_ptr=None, qM_ptr=None, qfrc_ptr=None, qacc_smooth_ptr=None, jac_ptr=None, snaps_ptr=None, n_snaps=1):
+        """The same pass on device pointers (float32: qM [n_snaps * N, 15, 15], qfrc [n_snaps * N, 3, 15] = bias | passive | actuator,
+        qacc_smooth [n_snaps * N, 15], jac [n_snaps * N, 14, 6, 15]; None = absent: no stores; ctrl None = 0), asynchronous.  snaps_ptr: a
+        stack of `n_snaps` device snapshots back to back (`snapshot_bytes` apart) instead of the current state; env-state k * N + j is env
+        j of snapshot k.  The result for one env-state does not depend on what else is in the launch, bit for bit."""
+        _lib.check(self._L.jb_inertia_device(self._h, snaps_ptr, int(n_snaps), ctrl_ptr, qM_ptr, qfrc_ptr, qacc_smooth_ptr, jac_ptr))
+
+    def foot_jacobians(self):
+        """float32 [N, 4, 3, 15]: the translational Jacobian (jacp, world axes) of each foot sphere's centre, in model_spec.LEG_NAMES order."""
+        return self.inertia(qM=False, qfrc=False, jac=True)["jac"][:, model.NBODY:, 0:3].copy()
+
     # ---- rows between GPUs through the library's own RCCL binding (jb_comm_*: no torch.distributed on the data path)
     @staticmethod
     def comm_unique_id():
