@@ -382,6 +382,34 @@ int jb_contacts(jb_handle* h, const float* ctrl /*[N] nullable*/, float* contact
 int jb_inertia_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_snaps, const float* d_ctrl /*[n_snaps*N] nullable*/, float* d_qM /*[n_snaps*N,15,15]*/,
                       float* d_qfrc /*[n_snaps*N,3,15]*/, float* d_qacc_smooth /*[n_snaps*N,15]*/, float* d_jac /*[n_snaps*N,JB_NJAC,6,15]*/);
 int jb_inertia(jb_handle* h, const float* ctrl /*[N] nullable*/, float* qM /*[N,15,15]*/, float* qfrc /*[N,3,15]*/, float* qacc_smooth /*[N,15]*/, float* jac /*[N,JB_NJAC,6,15]*/);
+/* Evaluate (additive in ABI 5): the task layer over any state, any task and any target.  One launch maps a state - the handle's current
+ * one, or a stack of snapshots - to what the task layer makes of it, per env-state, in fp32:
+ *   obs      [jb_obs_dim(task)]  the observation row of `task`, dense rows
+ *   reward   [1]                 the reward of `task`
+ *   terms    [4]                 [P, H, V, U], the position, heading, velocity and upright terms as jb_reward_terms gives them
+ *   achieved [3]                 (px, py, yaw): the goal the state attains, in the target's own coordinates.  px, py: the root position's
+ *                                words; yaw = wrap(atan2(R10, R00) - pi / 2) into (-pi, pi], R the root's rotation - the heading the
+ *                                target's yaw is compared with, so a target (px, py, yaw) is reached in position (up to the height of
+ *                                the target above the floor) and gives a relative angle of zero up to rounding.
+ * from the state words jb_observe reads (the high words of the height and the quaternion, the wrapped motor angle) and the constant tables
+ * the handle holds (one shared, or one per env).  On the same state, task and target the rows are jb_observe_device's,
+ * jb_reward_terms_device's and the step kernels' BIT FOR BIT, whichever step kernel the handle runs.  The pass reads the state and never
+ * writes it: the stored target, the counters and the warm start stay as they are.
+ *   task_id    0 .. 4, or -1 = the handle's own; one task for the whole launch
+ *   d_targets  [n_snaps * N, 3] = (tx, ty, tpsi) per env-state, or NULL = the target stored in each state.  The stored target's meaning
+ *              differs by task (move_from_origin: zeros; face_direction, move_in_direction: the yaw alone; move_to_position: the position
+ *              alone; move_to_pose: both), so a task other than the handle's own needs explicit targets (move_from_origin: pass zeros).
+ *   jb_evaluate_device  d_snaps: n_snaps snapshots of N envs each, back to back (jb_snapshot_bytes apart), or NULL = the handle's current
+ *                      state (n_snaps must then be 1).  Env-state k * N + j is env j of snapshot k and takes env j's table.  Each output
+ *                      is device memory for n_snaps * N env-states, or NULL: an absent output costs no stores.  The result for one
+ *                      env-state does not depend on what else is in the launch.  Asynchronous on the handle's stream.  JB_E_INVALID,
+ *                      and nothing is launched: n_snaps < 1, d_snaps == NULL with n_snaps != 1, all four outputs NULL, a jb_step_async
+ *                      pending, task_id outside -1 .. 4, d_targets == NULL with a task_id that is neither -1 nor the handle's own.
+ *   jb_evaluate         host buffers (targets [N, 3] or NULL; each output nullable, not all), the current state, synchronous; the device
+ *                      staging belongs to the handle, only grows, and is freed by jb_release_staging. */
+int jb_evaluate_device(jb_handle* h, const void* d_snaps /*nullable*/, int32_t n_snaps, int32_t task_id /* -1 = the handle's */, const float* d_targets /*[n_snaps*N,3] nullable*/,
+                       float* d_obs /*[n_snaps*N, jb_obs_dim(task)]*/, float* d_reward /*[n_snaps*N]*/, float* d_terms /*[n_snaps*N,4]*/, float* d_achieved /*[n_snaps*N,3]*/);
+int jb_evaluate(jb_handle* h, int32_t task_id, const float* targets /*[N,3] nullable*/, float* obs /*[N, jb_obs_dim(task)]*/, float* reward /*[N]*/, float* terms /*[N,4]*/, float* achieved /*[N,3]*/);
 /* seconds each wave of the LAST step launch was alive (one wave = jb_envs_per_wave envs), out[0 .. min(n_waves, max_waves)); returns the
  * number of waves.  Mean against maximum is the load imbalance of the launch (roofline). */
 int jb_wave_clocks(jb_handle* h, double* out, int32_t max_waves);

@@ -31,6 +31,7 @@
 #include "jb_owned.hpp"
 #include "jb_readout.hpp"
 #include "jb_inertia.hpp"
+#include "jb_evaluate.hpp"
 #include "jb_sim.hpp"
 #include "jb_snapshot.hpp"
 #include "jb_step.hpp"
@@ -950,6 +951,7 @@ struct jb_handle {
     Dev<unsigned char> d_done_stage;                   // jb_score_tapes_device: the done flags of every step, next to d_rew_stage (grow-only)
     Dev<float> d_readout_stage;                        // jb_readout: the outputs on their way to the host (grow-only)
     Dev<float> d_inertia_stage;                        // jb_inertia: the actions and the outputs on their way (grow-only)
+    Dev<float> d_evaluate_stage;                       // jb_evaluate: the targets and the outputs on their way (grow-only)
     Dev<float> d_contacts_stage;                       // jb_contacts: likewise
     Dev<float> d_forward_stage;                        // jb_forward: the actions on their way in, the outputs on their way out (grow-only)
     Dev<uint32_t> d_snap_stage; Dev<int> d_src_stage;  // jb_snapshot / jb_restore: the raw blocks and the index map on their way to / from the host (grow-only)
@@ -1515,7 +1517,7 @@ int jb_release_staging(jb_handle* h) {
     JB_ENTER(h);
     JB_HIP(hipStreamSynchronize(h->stream));
     h->d_tape.reset(); h->d_rows_stage.reset(); h->d_rew_stage.reset(); h->d_done_stage.reset();
-    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset(); h->d_inertia_stage.reset(); h->d_forward_stage.reset(); h->d_contacts_stage.reset();
+    h->d_snap_stage.reset(); h->d_src_stage.reset(); h->d_readout_stage.reset(); h->d_inertia_stage.reset(); h->d_evaluate_stage.reset(); h->d_forward_stage.reset(); h->d_contacts_stage.reset();
     return JB_OK;
 }
 // ---------------------------------------------------------------------------------------------- snapshot / restore / fork, tape scoring
@@ -1772,6 +1774,47 @@ int jb_inertia(jb_handle* h, const float* ctrl, float* qM, float* qfrc, float* q
     int rc = check_pass(h, "jb_inertia", nullptr, 1, qM || qfrc || qacc_smooth || jac, "four");
     if (!rc) rc = stage_parts(h, h->d_inertia_stage, part, "the inertia pass");
     if (!rc) rc = jb_inertia_device(h, nullptr, 1, part[4].dev<float>(), part[1].dev<float>(), part[2].dev<float>(), part[3].dev<float>(), part[0].dev<float>());
+    return rc ? rc : fetch_parts(h, part);
+}
+// The evaluate pass (jb_evaluate.hpp): the readout's launch - n_snaps * N env-states, a quad of lanes each, one kernel for every handle; reads
+// the state and the targets, writes only its outputs.  What it refuses about the task, before anything is launched; *task: the task evaluated.
+static int check_evaluate_task(jb_handle* h, const std::string& fn, int task_id, bool has_targets, int* task) {
+    if (task_id < -1 || task_id > 4) return fail(JB_E_INVALID, fn + ": task_id " + std::to_string(task_id) + " is outside -1 .. 4");
+    if (task_id != -1 && task_id != h->cfg.task_id && !has_targets)
+        return fail(JB_E_INVALID, fn + ": a task other than the handle's own needs explicit targets (the stored target's meaning differs by task)");
+    *task = task_id < 0 ? h->cfg.task_id : task_id;
+    return JB_OK;
+}
+int jb_evaluate_device(jb_handle* h, const void* d_snaps, int32_t n_snaps, int32_t task_id, const float* d_targets, float* d_obs, float* d_reward, float* d_terms, float* d_achieved) {
+    JB_ENTER(h);
+    EvArgs a;
+    int rc = check_pass(h, "jb_evaluate_device", d_snaps, n_snaps, d_obs || d_reward || d_terms || d_achieved, "four", &a.first);
+    if (!rc) rc = check_evaluate_task(h, "jb_evaluate_device", task_id, d_targets != nullptr, &a.task);
+    if (rc) return rc;
+    RoctxRange range("jb_evaluate");
+    const int N = h->cfg.n_envs;
+    a.stride_words = (long long)SNAP_WORDS * N;
+    a.total = (long long)n_snaps * N;
+    a.tab = h->ka.lane_model; a.n_tab = h->ka.per_env_model ? N : 1;
+    a.targets = d_targets;
+    a.obs = d_obs; a.reward = d_reward; a.terms = d_terms; a.achieved = d_achieved;
+    const long long blocks = (a.total + RO_EPB - 1) / RO_EPB;
+    rc = check_grid("jb_evaluate_device", blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL(jb_evaluate_kernel, dim3((unsigned)blocks), dim3(64), 0, h->stream, a);
+    JB_HIP(hipGetLastError());
+    return JB_OK;
+}
+int jb_evaluate(jb_handle* h, int32_t task_id, const float* targets, float* obs, float* reward, float* terms, float* achieved) {
+    JB_ENTER(h);
+    const size_t F = sizeof(float) * (size_t)h->cfg.n_envs;
+    int task = 0;
+    int rc = check_pass(h, "jb_evaluate", nullptr, 1, obs || reward || terms || achieved, "four");
+    if (!rc) rc = check_evaluate_task(h, "jb_evaluate", task_id, targets != nullptr, &task);
+    if (rc) return rc;
+    StagePart part[] = {{obs, F * (size_t)obs_dim(task)}, {reward, F}, {terms, F * EV_TERMS}, {achieved, F * EV_GOAL}, {const_cast<float*>(targets), F * EV_GOAL, true}};
+    rc = stage_parts(h, h->d_evaluate_stage, part, "the evaluate pass");
+    if (!rc) rc = jb_evaluate_device(h, nullptr, 1, task, part[4].dev<float>(), part[0].dev<float>(), part[1].dev<float>(), part[2].dev<float>(), part[3].dev<float>());
     return rc ? rc : fetch_parts(h, part);
 }
 // how long each wave of the last step launch lived, in seconds (s_memrealtime, 100 MHz): out[0 .. n_waves); returns the number of waves

@@ -180,6 +180,14 @@ class Physics:
         out = self._venv.inertia(a, qM=True, qfrc=True, qacc_smooth=True, jac=True)
         return {k: v[self._i].copy() for k, v in out.items()}
 
+    def evaluate(self, task=None, target=None):
+        """What the task layer makes of this env's current state under `task` (a task name; None: the env's own) and `target` =
+        (tx, ty, tpsi) (None: the stored one, only with the env's own task): JitterbugVecEnv.evaluate's dict with every output - 'obs'
+        [D(task)], 'reward' (a float), 'terms' [4] = [P, H, V, U], 'achieved' [3] = (px, py, yaw) - float32.  With the defaults, 'obs' and
+        'reward' are the observation and the reward of the env's own task, bit for bit.  Nothing is written: the stored target stays."""
+        out = self._venv.evaluate(task, None if target is None else np.asarray(target, dtype=np.float32).reshape(3), obs=True, reward=True, terms=True, achieved=True)
+        return {k: (float(v[self._i]) if k == "reward" else v[self._i].copy()) for k, v in out.items()}
+
     def jacobian(self, name):
         """(jacp [3, 15], jacr [3, 15]) of `name` in model.JAC_NAMES - a body at its centre of mass (mj_jacBodyCom) or a foot sphere's
         centre (mj_jacGeom) - in world axes, for this env's current state.  KeyError: no such name.  Every call runs the batch's pass and

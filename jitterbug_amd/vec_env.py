@@ -609,6 +609,50 @@ class JitterbugVecEnv:
         """float32 [N, 4, 3, 15]: the translational Jacobian (jacp, world axes) of each foot sphere's centre, in model_spec.LEG_NAMES order."""
         return self.inertia(qM=False, qfrc=False, jac=True)["jac"][:, model.NBODY:, 0:3].copy()
 
+    # ---- evaluate: the task layer over any state, task and target (jb_evaluate / jb_evaluate_device)
+    @staticmethod
+    def _task_index(task):
+        """-1 for None (the env's own task), else the index of a task name or a valid index itself"""
+        if task is None:
+            return -1
+        if isinstance(task, str):
+            if task not in TASKS:
+                raise ValueError("Invalid task {}, options are {}".format(task, list(TASKS)))
+            return TASKS.index(task)
+        return int(task)
+
+    def evaluate(self, task=None, targets=None, obs=True, reward=True, terms=False, achieved=False):
+        """What the task layer makes of the current state under `task` (a name of TASKS or its index; None: the env's own) and `targets`
+        ([N, 3] or [3] = (tx, ty, tpsi); None: the stored ones - only with the env's own task, the stored target's meaning differs by
+        task), as a dict of float32 arrays, one row per env (only the outputs asked for): 'obs' [N, D(task)], 'reward' [N], 'terms'
+        [N, 4] = [P, H, V, U] as reward_terms() gives them, 'achieved' [N, 3] = (px, py, yaw), the goal the state attains in the target's
+        coordinates.  With the env's own task and target the rows are observe()'s and reward_terms()' bit for bit.  The pass reads the
+        state and never writes it: target, counters and warm start stay."""
+        n, tid = self.num_envs, self._task_index(task)
+        t = None if targets is None else np.ascontiguousarray(np.broadcast_to(np.asarray(targets, dtype=np.float32), (n, 3)))
+        out = {}
+        if obs:
+            out["obs"] = np.empty((n, model.OBS_DIM[TASKS[tid]] if 0 <= tid < len(TASKS) else self.obs_dim), dtype=np.float32)
+        if reward:
+            out["reward"] = np.empty(n, dtype=np.float32)
+        if terms:
+            out["terms"] = np.empty((n, 4), dtype=np.float32)
+        if achieved:
+            out["achieved"] = np.empty((n, 3), dtype=np.float32)
+        _lib.check(self._L.jb_evaluate(self._h, tid, _lib.ptr(t), _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("terms")), _lib.ptr(out.get("achieved"))))
+        return out
+
+    def evaluate_device(self, task=None, targets_ptr=None, obs_ptr=None, reward_ptr=None, terms_ptr=None, achieved_ptr=None, snaps_ptr=None, n_snaps=1):
+        """The same pass on device pointers (float32: targets [n_snaps * N, 3] or None = the stored ones, obs [n_snaps * N, D(task)] dense
+        rows, reward [n_snaps * N], terms [n_snaps * N, 4], achieved [n_snaps * N, 3]; None = absent: no stores), asynchronous.  snaps_ptr:
+        a stack of `n_snaps` device snapshots back to back (`snapshot_bytes` apart) instead of the current state; env-state k * N + j is
+        env j of snapshot k.  The result for one env-state does not depend on what else is in the launch, bit for bit."""
+        _lib.check(self._L.jb_evaluate_device(self._h, snaps_ptr, int(n_snaps), self._task_index(task), targets_ptr, obs_ptr, reward_ptr, terms_ptr, achieved_ptr))
+
+    def achieved_goals(self):
+        """float32 [N, 3] = (px, py, yaw): the goal each env's current state attains, in the target's coordinates (evaluate()'s 'achieved')."""
+        return self.evaluate(obs=False, reward=False, achieved=True)["achieved"]
+
     # ---- rows between GPUs through the library's own RCCL binding (jb_comm_*: no torch.distributed on the data path)
     @staticmethod
     def comm_unique_id():
